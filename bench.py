@@ -1,6 +1,6 @@
 """Benchmark: env-steps/s of T1DHStandEnv.step() (the LeggedRobot.step() hot path) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--num-envs 8192] [--mesh trimesh]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--num-envs 8192] [--mesh trimesh] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -19,7 +19,10 @@ pmc_traffic.py).  Per-kernel durations are measured live with HIP events around 
 algorithmic bytes; the dominant kernel is the whole fused step -- k_dyn6 (eight role waves, two per SIMD; latency-bound
 on its core wave's chain) at every config but config 5's fp16 histories, where t1env picks k_dyn4 with its
 history shift as a concurrent launch (fused_kernel below names the kernel of each run).
+A plain run sets up, warms up, times the K steps (the per-kernel events ride on those same steps) and prints the line;
+--full adds what takes a run of its own:
 cpu_baseline: the build's CPU restatement (numpy oracle post-physics + OpenMP dynamics), rank 0, N = 1 only.
+--dump-outputs DIR: what the last timed step returned, as DIR/<name>.npy (dump_outputs below).
 """
 import argparse
 import json
@@ -46,6 +49,8 @@ SIMD_VALU_PER_CYCLE = 0.5        # a SIMD with two or more waves: one wave64 VAL
 # whole fused step (k_dyn6: dynamics + in-workgroup history shift + post-physics epilogue, t1env_dyn6.hip);
 # k_post_a / k_post_b only launch on the split (command-curriculum, 1 in 2400) steps
 KERNELS = ["k_dynamics", "k_post_a", "k_post_b"]
+DUMP_BYTES = 48 << 20  # --dump-outputs: cap on the per-env arrays together (8192 envs' 3102-float obs alone are 97 MiB)
+DUMP_SEED = 20240    # ... and the seed of the env sample that keeps them under it
 def fused_kernel(num_envs, cus=256, obs_half=False):
     """The step kernel t1env picks (t1_dyn_waves_default): k_dyn6, k_dyn4 for fp16 histories above one round of 32-env
     workgroups; the T1ENV_DYN_KERNEL override wins."""
@@ -84,7 +89,13 @@ def parse():
     p.add_argument("--repeats", type=int, default=1,
                    help="time the K steps R times (each bracketed by barrier + synchronize) and report the median "
                         "(SURVEY §8(d): median of 5); the per-repeat values go to repeat_values")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the CPU baseline (N = 1).  A plain run sets "
+                        "up, warms up, times the K steps and prints the line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed env.step() returned as DIR/<name>.npy "
+                        "(float32; a fixed seeded sample of the envs when all of them would pass DUMP_BYTES)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     p.add_argument("--no-self-collision", action="store_true",
                    help="A/B only (not the metric's config): asset.self_collisions = 1 (Isaac Gym's filter: disabled)")
     p.add_argument("--time-every", type=int, default=8,
@@ -167,6 +178,32 @@ def cpu_baseline(env, args):
                       f"threads on the {aff} cores this process may use (affinity capped by the cgroup CPU quota), {model}"}
 
 
+def dump_outputs(env, out_dir):
+    """--dump-outputs: what the last env.step() returned to its caller (the reference's 5-tuple: observations,
+    privileged observations, rewards, resets, extras) plus the root states, one float32 DIR/<name>.npy each.  The env
+    and the action pool are seeded, so two runs with the same arguments step the same inputs and their files compare
+    array for array.  When every env's rows would pass DUMP_BYTES, a fixed seeded sample of the envs is kept (the same
+    rows of every per-env array, listed in env_rows.npy)."""
+    obs, priv, rew, reset, extras = env.obs_buf, env.privileged_obs_buf, env.rew_buf, env.reset_buf, env.extras
+    per_env = {"obs": obs, "privileged_obs": priv, "rew": rew, "reset": reset, "root_states": env.root_states}
+    if "time_outs" in extras:
+        per_env["time_outs"] = extras["time_outs"]
+    n = env.num_envs
+    row_bytes = sum(4 * (t.numel() // n) for t in per_env.values())
+    keep = min(n, DUMP_BYTES // row_bytes)
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False)) if keep < n else np.arange(n)
+    idx = torch.as_tensor(rows, device=obs.device)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in per_env.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.index_select(0, idx).to(torch.float32).cpu().numpy())
+    np.save(os.path.join(out_dir, "env_rows.npy"), rows.astype(np.float64))
+    ep = extras.get("episode", {})
+    keys = sorted(k for k in ep if torch.is_tensor(ep[k]))   # the per-reward episode means (0-d device views)
+    if keys:
+        np.save(os.path.join(out_dir, "extras_episode.npy"),
+                torch.stack([ep[k].to(torch.float32) for k in keys]).cpu().numpy())
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -227,6 +264,8 @@ def main():
         reps.append(el)
     kt = env.get_timing()
     env.set_timing(False)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(env, args.dump_outputs)
     elapsed = sorted(reps)[len(reps) // 2]  # the median repeat (the only one at --repeats 1)
     ok = bool(torch.isfinite(env.root_states).all() and torch.isfinite(env.obs_buf).all())
     dist_info = {"backend": "none", "world_size": 1, "env_offsets": [env.env_offset]}
@@ -370,7 +409,7 @@ def main():
     if len(reps) > 1:
         line["repeats"] = len(reps)
         line["repeat_values"] = [round(N * world * steps / e, 1) for e in reps]
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(env, args)
     print(json.dumps(line), flush=True)
     if world > 1:

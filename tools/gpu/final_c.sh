@@ -10,4 +10,4 @@ timeout -k 10 300 python tools/act_bench.py > $out/act.json 2> $out/act.err
 cat $out/act.json
 timeout -k 10 300 python tools/bench_ppo.py --iters 4 > $out/ppo_fp32.json 2> $out/ppo.err
 timeout -k 10 300 python tools/bench_ppo.py --iters 4 --bf16 > $out/ppo_bf16.json 2>> $out/ppo.err
-timeout -k 10 300 python bench.py > $out/bench_default.json 2> $out/bench_default.err
+timeout -k 10 300 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
