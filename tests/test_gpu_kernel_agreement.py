@@ -1,6 +1,6 @@
 """The selectable step kernels agree with each other -- needs the MI355X.
 
-The product runs k_dyn6 at every env count (t1_dyn_waves_default, since r05; until r04 the choice went by env count,
+The product runs k_dyn6 at every env count (t1_dyn_kernel_default, since r05; until r04 the choice went by env count,
 so the same global envs ran on different kernels in an 8-GPU run and on one GPU), and T1ENV_DYN_KERNEL=4|5 selects
 the older kernels.  The kernels solve
 the same linear system per substep (compute_delta / _split / _roles / _roles6 agree in fp64, tests/test_dynamics.py)

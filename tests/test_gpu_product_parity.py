@@ -1,7 +1,7 @@
 """Pin the PRODUCT step kernels against the oracle at BASELINE sizes -- needs the MI355X.
 
 The product's fused step is k_dyn6 (eight role waves, t1env_dyn6.hip) at every config except config 5's fp16 histories,
-where t1env picks k_dyn4 (t1_dyn_waves_default); k_dyn5 stays selectable (T1ENV_DYN_KERNEL).  Every case below runs for
+where t1env picks k_dyn4 (t1_dyn_kernel_default); k_dyn5 stays selectable (T1ENV_DYN_KERNEL).  Every case below runs for
 each of them (the dyn_kernel fixture of conftest.py).
 
 The golden fixtures pin post-physics through the injected-physics test hook (k_physics_injected, test_gpu_parity.py).

@@ -28,7 +28,7 @@
 
 #include "t1_common.h"
 
-// phase profiling hook (t1env_dynamics.hip built with -DT1_PHASE_PROF); compiled out otherwise
+// phase profiling hook (t1env_prof.h, which the step kernels' units include first); compiled out otherwise
 #ifndef T1_PROF_MARK
 #define T1_PROF_MARK(i) ((void)0)
 #endif
@@ -288,11 +288,6 @@ template <typename R> T1_HD void motion_subspace(const DynModel& M, int b, const
 }
 
 // world inertia about COM (xx yy zz xy xz yz) of body b
-// timing-only what-if builds (never the product): the body-frame inertia used as if the body were unrotated
-template <typename R> T1_HD void world_inertia_unrotated(const DynModel& M, int b, R scale, R out[6]) {
-#pragma unroll
-  for (int i = 0; i < 6; ++i) out[i] = scale * R(M.inertia[b][i]);
-}
 template <typename R>
 T1_HD void world_inertia(const DynModel& M, int b, const M3<R>& Rb, R scale, R out[6]) {
   const float* I = M.inertia[b];
@@ -354,9 +349,6 @@ template <typename R> T1_HD void moments_flush(const PointMoments<R>& P, Sym6<R>
 // compliant law's own rebound (the spring's stored energy) comes on top: the exit speed is at least ~e v_imp.
 // v_tgt = 0 is the plain compliant law.
 template <typename R> T1_HD R restitution_target(const DynModel& M, R e, R vimp) {
-#ifdef T1_WHATIF_NO_RESTITUTION  // timing-only what-if build: no restitution set point
-  return R(0);
-#endif
   return vimp > R(M.bounce_threshold) ? e * vimp : R(0);
 }
 // the episode after this substep: amax = the fastest approach among the body's points in contact (< 0: none)
@@ -481,9 +473,7 @@ __device__ __forceinline__ void pair_acc_flush(const PairAcc& P, Sym6<float>& A,
 // in between, so all coordinate (scalar) and height-field (vector) loads issue together and the body pays
 // one memory latency instead of one per point; phase 2 runs the contact math for the points in contact
 // (on the device in fp32: two points per packed instruction, contact_pair).
-#ifndef T1_CONTACT_BATCH
-#define T1_CONTACT_BATCH 8
-#endif
+constexpr int T1_CONTACT_BATCH = 8;
 template <bool HF, int NP, typename R>
 T1_HD void body_contact_np(const DynModel& M, const Terrain& T, int c_begin, const M3<R>& Rb, V3<R> pb,
                            V3<R> base_abs, const R Vb[6], R mu, R vtg, R dt, Sym6<R>& A, R g[6], R& amax) {
@@ -491,7 +481,7 @@ T1_HD void body_contact_np(const DynModel& M, const Terrain& T, int c_begin, con
   static_assert(NP % CH == 0, "contact points per body must be a multiple of the batch");
   PointMoments<R> fric;
   moments_zero(fric);
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(T1_SCALAR_CONTACT)
+#if defined(__HIP_DEVICE_COMPILE__)
   PairAcc pacc;
   if constexpr (std::is_same<R, float>::value && CH % 2 == 0) pair_acc_zero(pacc);
 #endif
@@ -511,7 +501,7 @@ T1_HD void body_contact_np(const DynModel& M, const Terrain& T, int c_begin, con
     __builtin_amdgcn_s_waitcnt(0);  // profiling build: separate the height loads' latency from the math
     T1_PROF_MARK(17);
 #endif
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(T1_SCALAR_CONTACT)
+#if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (std::is_same<R, float>::value && CH % 2 == 0) {
 #pragma unroll
       for (int i = 0; i < CH; i += 2) {
@@ -537,13 +527,13 @@ T1_HD void body_contact_np(const DynModel& M, const Terrain& T, int c_begin, con
     }
     T1_PROF_MARK(18);
   }
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(T1_SCALAR_CONTACT)
+#if defined(__HIP_DEVICE_COMPILE__)
   if constexpr (std::is_same<R, float>::value && CH % 2 == 0) pair_acc_flush(pacc, A, g);
 #endif
   moments_flush(fric, A);
 }
 
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(T1_SCALAR_CONTACT)
+#if defined(__HIP_DEVICE_COMPILE__)
 // one pair of queried points into the pair accumulators (contact_apply), every input by value
 template <bool HF>
 __device__ __forceinline__ void contact_pair_q(const DynModel& M, V3<float> x0, V3<float> x1, float dz0, float dz1,
@@ -581,7 +571,7 @@ T1_HD void contact_apply(const DynModel& M, const ContactQuery<NP, R>& Q, const 
                          R g[6], R& amax) {
   PointMoments<R> fric;
   moments_zero(fric);
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(T1_SCALAR_CONTACT)
+#if defined(__HIP_DEVICE_COMPILE__)
   if constexpr (std::is_same<R, float>::value && NP % 2 == 0) {
     PairAcc pacc;
     pair_acc_zero(pacc);
@@ -1422,11 +1412,7 @@ T1_HD void leg_forward_nc(const DynModel& M, const LegParams<R>& P, const BaseFr
     for (int i = 0; i < 6; ++i) A[i] += cr[i];
     if constexpr ((CM >> k) & 1) pub(kc, Rk, pk, V);
     R Icw[6];
-#ifdef T1_WHATIF_FWD_NOROT
-    world_inertia_unrotated(M, b, P.inertia_scale[k], Icw);
-#else
     world_inertia(M, b, Rk, P.inertia_scale[k], Icw);
-#endif
     const V3<R> c = pk + mul(Rk, v3<R>(M.com[b][0], M.com[b][1], M.com[b][2]));
     rnea_bias_com(P.mass[k], c, Icw, V, A, dt, st.g[k]);
   };
@@ -1540,11 +1526,7 @@ T1_HD void leg_backward_nc(const DynModel& M, const LegParams<R>& P, const R q[N
     joint_subspace<T1_LEG_AXIS[k]>(M, b, Rk, pk, Sk);
     {
       R Icw[6];
-#ifdef T1_WHATIF_BWD_NOROT
-      world_inertia_unrotated(M, b, P.inertia_scale[k], Icw);
-#else
       world_inertia(M, b, Rk, P.inertia_scale[k], Icw);
-#endif
       const V3<R> c = pk + mul(Rk, v3<R>(M.com[b][0], M.com[b][1], M.com[b][2]));
       composite_add(Ac, P.mass[k], c, Icw);
     }

@@ -61,7 +61,7 @@ struct t1env {
   DynModel* d_model;
   t1env_config* d_cfg;
   Terrain terrain;
-  DynLaunch dyn;          // dynamics kernel shape (T1ENV_DYN_WAVES / T1ENV_SHIFT_BLOCKS override; tuning)
+  DynLaunch dyn;          // step kernel and shift shape (T1ENV_DYN_KERNEL / T1ENV_SHIFT_BLOCKS override; tuning)
   int shift_pending;      // phase A enqueued this step's history shift (phase B alone must run it)
   int fused;              // t1env_step runs the single fused launch (t1env_set_fused; default on)
   uint32_t epoch;         // fused launches so far (tags the shift-unit handoff words)
@@ -182,9 +182,7 @@ __global__ __launch_bounds__(256) void k_shift(ShiftArgs S) {
 
 // chunks per lane in flight in the concurrent shift launch (k_shift5): 93 VGPRs at 4 (8 spills), so one of its waves fits beside
 // a k_dyn5 wave on every SIMD
-#ifndef T1_D5_SHIFT_UNROLL
-#define T1_D5_SHIFT_UNROLL 4
-#endif
+constexpr int T1_D5_SHIFT_UNROLL = 4;
 // ---------------------------------------------------------------------------------------------------
 // k_shift5 (compiled here at -O3; the dynamics unit's -O1 spilled its 64-bit addresses): the history shift as a launch of its own, on a second stream beside k_dyn5 (DynLaunch::d5_shift = 1).
 // One 256-thread workgroup per CU with no LDS but its handoff words and <= 96 VGPRs per wave, so it fits next to
@@ -232,9 +230,7 @@ void k_shift5(ShiftArgs S, FusedArgs FA, int N) {
 // k_shift4c: the same concurrent shift beside k_dyn4 (config 5: 32768 envs, fp16 histories).  A k_dyn4
 // wave holds 433 of a SIMD's 512 registers per lane, so a shift wave must stay within 72 (amdgpu_waves_per_eu(7, 8)) to
 // share the SIMD; its 148 KB of LDS leaves room for the shift's 1 KB of handoff words.
-#ifndef T1_D4_SHIFT_UNROLL
-#define T1_D4_SHIFT_UNROLL 3
-#endif
+constexpr int T1_D4_SHIFT_UNROLL = 3;
 template <bool FUSED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8)))
 void k_shift4c(ShiftArgs S, FusedArgs FA, int N) {
@@ -459,8 +455,8 @@ const char* t1env_last_error(void) { return g_err; }
 #endif
 const char* t1env_version(void) { return "t1env-hip 0.1 (gfx950) src:" T1_SOURCE_STAMP; }
 
-// one EP_PART_ROW-float row per k_dyn4 dynamics workgroup
-// one row per dynamics workgroup: k_dyn5 has 32 envs per workgroup (k_dyn4 64)
+// one EP_PART_ROW-float row per dynamics workgroup, sized for the most workgroups: k_dyn5 / k_dyn6 have 32 envs per
+// workgroup (k_dyn4 64)
 static size_t ep_part_bytes(int num_envs) { return sizeof(float) * EP_PART_ROW * (size_t)((num_envs + 31) / 32); }
 
 int t1env_create(const t1env_model* model, const t1env_config* cfg, const t1env_buffers* bufs, t1env** out) {
@@ -506,9 +502,9 @@ int t1env_create(const t1env_model* model, const t1env_config* cfg, const t1env_
     if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
         hipSuccess) cus = 256;
     e->dyn.cus = cus;
-    e->dyn.waves = t1_dyn_waves_default(cfg->num_envs, cus, cfg->obs_half != 0);
+    e->dyn.kernel = t1_dyn_kernel_default(cfg->num_envs, cus, cfg->obs_half != 0);
     if (const char* dk = getenv("T1ENV_DYN_KERNEL"))  // A/B: 4 = k_dyn4, 5 = k_dyn5, 6 = k_dyn6
-      if (atoi(dk) >= 4 && atoi(dk) <= 6) e->dyn.waves = atoi(dk);
+      if (atoi(dk) >= 4 && atoi(dk) <= 6) e->dyn.kernel = atoi(dk);
     e->dyn.shift_blocks = 0;
     if (const char* sb = getenv("T1ENV_SHIFT_BLOCKS"))  // > 0: shift workgroups in the launch; -1: stand-alone shift
       if (atoi(sb) > 0 || atoi(sb) == -1) e->dyn.shift_blocks = atoi(sb);
@@ -603,10 +599,10 @@ static int launch_shift(t1env* e, const t1env_step_args* a, hipStream_t s) {
 // enqueued on s so far (fork), runs the shift beside the dynamics launch, and s waits for it before anything after the
 // step (join).  The fused epilogue and the shift hand each 8-row unit off (the k_dyn4 protocol, t1env_fused.h).
 static bool concurrent_shift4(const t1env* e) {
-  return e->dyn.waves == 4 && e->dyn.d4_shift == 1 && t1_shift_prelaunch(e->cfg.num_envs, e->dyn);
+  return e->dyn.kernel == 4 && e->dyn.d4_shift == 1 && t1_shift_prelaunch(e->cfg.num_envs, e->dyn);
 }
 static bool concurrent_shift(const t1env* e) {
-  return (e->dyn.waves == 5 && e->dyn.d5_shift == 1) || concurrent_shift4(e);
+  return (e->dyn.kernel == 5 && e->dyn.d5_shift == 1) || concurrent_shift4(e);
 }
 static int shift_fork(t1env* e, hipStream_t s) {
   HIP_TRY(hipEventRecord(e->ev_fork, s));
@@ -616,10 +612,20 @@ static int shift_fork(t1env* e, hipStream_t s) {
 static int shift_join(t1env* e, const t1env_step_args* a, const FusedArgs* fa, hipStream_t s) {
   const int t = t_begin(e, 3, e->side);  // the shift's own span, on its stream (bench.py: k_shift)
   HIP_TRY((hipError_t)t1_launch_shift5(shift_args(e, a), fa, e->cfg.num_envs, e->dyn.cus, e->side,
-                                       e->dyn.waves == 4));
+                                       e->dyn.kernel == 4));
   t_end(e, t, e->side);
   HIP_TRY(hipEventRecord(e->ev_join, e->side));
   HIP_TRY(hipStreamWaitEvent(s, e->ev_join, 0));
+  return 0;
+}
+
+// Where the history shift does not run inside the dynamics launch (large N): its own launch ahead of the dynamics in
+// stream order (pre), or the fork of the side stream that runs it beside them (conc; shift_join after the dynamics)
+static int shift_before_dynamics(t1env* e, const t1env_step_args* a, bool pre, bool conc, hipStream_t s) {
+  if (pre && !conc)
+    if (int rc = launch_shift(e, a, s)) return rc;
+  if (conc)
+    if (int rc = shift_fork(e, s)) return rc;
   return 0;
 }
 
@@ -633,10 +639,7 @@ static int launch_physics(t1env* e, const float* actions, const t1env_step_args*
   // the join)
   const bool conc = !inj && concurrent_shift(e);
   const bool pre = !inj && t1_shift_prelaunch(N, e->dyn);
-  if (pre && !conc)
-    if (int rc = launch_shift(e, a, s)) return rc;
-  if (conc)
-    if (int rc = shift_fork(e, s)) return rc;
+  if (int rc = shift_before_dynamics(e, a, pre, conc, s)) return rc;
   int t = t_begin(e, 0, s);
   if (inj)
     hipLaunchKernelGGL(k_physics_injected, dim3(grid(N, BLOCK)), dim3(BLOCK), 0, s, e->d_model, e->d_cfg, e->buf,
@@ -699,10 +702,7 @@ static int launch_fused(t1env* e, const float* actions, const t1env_step_args* a
   // the epilogue hands its reset rows off) or first (the epilogue then zeroes them without the handoff)
   const bool conc = concurrent_shift(e);
   const bool pre = t1_shift_prelaunch(e->cfg.num_envs, e->dyn);
-  if (pre && !conc)
-    if (int rc = launch_shift(e, a, s)) return rc;
-  if (conc)
-    if (int rc = shift_fork(e, s)) return rc;
+  if (int rc = shift_before_dynamics(e, a, pre, conc, s)) return rc;
   const int t = t_begin(e, 0, s);
   const FusedArgs FA{e->d_done, e->d_unit_state, ++e->epoch, (pre && !conc) ? 1 : 0, e->d_ep_part};
   HIP_TRY((hipError_t)t1_launch_dynamics(e->d_model, e->d_cfg, e->buf, e->terrain, actions, *a, e->cfg.num_envs,
@@ -788,12 +788,10 @@ int t1env_get_timing(t1env* e, double* ms, int32_t* launches) {
   return 0;
 }
 
-int t1env_reset_all(t1env* e, const t1env_step_args* a, void* stream) {
-  if (!e || !a) return fail(T1ENV_E_ARG, "t1env_reset_all: null argument");
-  hipStream_t s = (hipStream_t)stream;
+// the launches of a reset: the envs of `mask` (nullptr: every env), the terrain-level sum, the extras
+static int launch_reset(t1env* e, const t1env_step_args* a, const uint8_t* mask, hipStream_t s) {
   const int N = e->cfg.num_envs;
-  hipLaunchKernelGGL(k_reset_all, dim3(grid(N, BLOCK)), dim3(BLOCK), 0, s, e->d_model, e->d_cfg, e->buf, *a,
-                     (const uint8_t*)nullptr);
+  hipLaunchKernelGGL(k_reset_all, dim3(grid(N, BLOCK)), dim3(BLOCK), 0, s, e->d_model, e->d_cfg, e->buf, *a, mask);
   HIP_TRY(hipGetLastError());
   if (e->cfg.custom_origins) {
     hipLaunchKernelGGL(k_terrain_level_sum, dim3(grid(N, 256)), dim3(256), 0, s, e->buf, e->d_cfg);
@@ -801,6 +799,14 @@ int t1env_reset_all(t1env* e, const t1env_step_args* a, void* stream) {
   }
   hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, e->buf, e->d_cfg, (int)(a->counter % T1ENV_EXTRAS_RING));
   HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int t1env_reset_all(t1env* e, const t1env_step_args* a, void* stream) {
+  if (!e || !a) return fail(T1ENV_E_ARG, "t1env_reset_all: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  const int N = e->cfg.num_envs;
+  if (int rc = launch_reset(e, a, nullptr, s)) return rc;
   // every history row restarts from zeros: clear both ping-pong buffers (the next step shifts from either)
   for (int k = 0; k < 2; ++k) {
     const size_t es = e->cfg.obs_half ? 2 : 4;
@@ -815,14 +821,7 @@ int t1env_reset_idx(t1env* e, const uint8_t* mask, const t1env_step_args* a, voi
   if (a->obs_slot & ~1) return fail(T1ENV_E_ARG, "t1env_reset_idx: obs_slot must be 0 or 1");
   hipStream_t s = (hipStream_t)stream;
   const int N = e->cfg.num_envs;
-  hipLaunchKernelGGL(k_reset_all, dim3(grid(N, BLOCK)), dim3(BLOCK), 0, s, e->d_model, e->d_cfg, e->buf, *a, mask);
-  HIP_TRY(hipGetLastError());
-  if (e->cfg.custom_origins) {
-    hipLaunchKernelGGL(k_terrain_level_sum, dim3(grid(N, 256)), dim3(256), 0, s, e->buf, e->d_cfg);
-    HIP_TRY(hipGetLastError());
-  }
-  hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, e->buf, e->d_cfg, (int)(a->counter % T1ENV_EXTRAS_RING));
-  HIP_TRY(hipGetLastError());
+  if (int rc = launch_reset(e, a, mask, s)) return rc;
   hipLaunchKernelGGL(k_zero_masked_rows, dim3(N), dim3(256), 0, s, e->buf.obs_buf[a->obs_slot],
                      e->buf.priv_buf[a->obs_slot], mask, N, e->cfg.obs_half ? 1 : 0);
   HIP_TRY(hipGetLastError());

@@ -28,52 +28,9 @@
 // and the reset rows, W1 the state stores and reset_idx, W2 the privileged frame and last_* rows, W3 the actor frame.
 #include <hip/hip_runtime.h>
 
-// -DT1_PHASE_PROF (tools/prof_dynamics_phases.py --kernel 5): lane 0 of every wave accumulates shader-clock deltas
-// between T1_PROF_MARK points into per-phase buckets; never part of the product build.
-#ifdef T1_PHASE_PROF
-constexpr int T1_NPROF5 = 24, T1_PROF_WAVES5 = 4;
-__device__ unsigned long long g_t1_prof5[T1_PROF_WAVES5][T1_NPROF5];
-__shared__ unsigned long long t1_prof_acc5[T1_PROF_WAVES5][T1_NPROF5 + 1];  // [wave][bucket], last = previous mark
-__device__ __forceinline__ unsigned long long t1_stamp5() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-__device__ __forceinline__ void t1_prof_mark5(int i) {
-  const int w = threadIdx.x / 64;
-  const unsigned long long now = t1_stamp5();
-  if ((threadIdx.x & 63) == 0) {
-    t1_prof_acc5[w][i] += now - t1_prof_acc5[w][T1_NPROF5];
-    t1_prof_acc5[w][T1_NPROF5] = now;
-  }
-}
-__device__ __forceinline__ void t1_prof_begin5() {
-  const int w = threadIdx.x / 64;
-  if ((threadIdx.x & 63) == 0) {
-    for (int i = 0; i < T1_NPROF5; ++i) t1_prof_acc5[w][i] = 0;
-    t1_prof_acc5[w][T1_NPROF5] = t1_stamp5();
-  }
-}
-__device__ __forceinline__ void t1_prof_end5() {
-  const int w = threadIdx.x / 64;
-  if ((threadIdx.x & 63) == 0)
-    for (int i = 0; i < T1_NPROF5; ++i) atomicAdd(&g_t1_prof5[w][i], t1_prof_acc5[w][i]);
-}
-#define T1_PROF_MARK(i) t1_prof_mark5(i)
-#define T1_PROF_BEGIN() t1_prof_begin5()
-#define T1_PROF_END() t1_prof_end5()
-#elif defined(T1_ASM_MARKS)  // ISA analysis build (tools/isa_phases.py): the marks as assembly comments
-#define T1_ASM_STR2(x) #x
-#define T1_ASM_STR(x) T1_ASM_STR2(x)
-#define T1_PROF_MARK(i) asm volatile(";@@MARK " #i "@L" T1_ASM_STR(__LINE__))
-#define T1_PROF_BEGIN() asm volatile(";@@MARK begin")
-#define T1_PROF_END() asm volatile(";@@MARK end")
-#else
-#define T1_PROF_BEGIN() ((void)0)
-#define T1_PROF_END() ((void)0)
-#endif
+#define T1_PROF_WAVES 4
+#define T1_PROF_NAME(x) x##5
+#include "t1env_prof.h"  // T1_PROF_MARK / _BEGIN / _END (tools/prof_dynamics_phases.py --kernel 5, tools/isa_phases.py)
 
 #include "t1_dyn5.h"
 #include "t1env_device.h"
@@ -290,9 +247,6 @@ __device__ __forceinline__ void shift_glds_slice(const ShiftArgs& S, int64_t r0,
 }
 __device__ __forceinline__ void shift_glds(const ShiftArgs& S, int64_t r0, int64_t r1, int sl, int nsl, int w, int lane,
                                            ShiftRing& R, bool commit) {
-#ifdef T1_WHATIF_D5_NO_SHIFT  // timing-only what-if build: the history is not shifted
-  return;
-#endif
   if (S.half) shift_glds_slice<true>(S, r0, r1, sl, nsl, w, lane, R, commit);
   else shift_glds_slice<false>(S, r0, r1, sl, nsl, w, lane, R, commit);
 }
@@ -320,11 +274,7 @@ __global__ __launch_bounds__(D5_BLOCK) void k_dyn5(const DynModel* __restrict__ 
   const t1env_config& C = *Cp;
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / 64);
   const int lane = threadIdx.x & 63;
-#ifdef T1_WHATIF_D5_SCALAR_MODEL  // timing-only what-if: every lane runs the left leg's model through scalar loads
-  const int leg = 0;
-#else
   const int leg = lane >> 5;
-#endif
   const int e = lane & 31;
   const int j0 = 6 * leg;
   const int N = C.num_envs;
@@ -337,11 +287,7 @@ __global__ __launch_bounds__(D5_BLOCK) void k_dyn5(const DynModel* __restrict__ 
   const int64_t r0 = (int64_t)blockIdx.x * NE5, r1 = r0 + NE5 < N ? r0 + NE5 : N;
   T1_PROF_BEGIN();
   __syncthreads();  // the model in LDS
-#ifdef T1_WHATIF_D5_SCALAR_MODEL
-  const DynModel& M = *Mg;
-#else
   const DynModel& M = lds.model;
-#endif
 
   if (wave == 1) {
     // ---------------- W1: RNEA bias terms of the leg, both base-box halves
@@ -646,10 +592,7 @@ __global__ __launch_bounds__(D5_BLOCK) void k_dyn5(const DynModel* __restrict__ 
   const RngKey K = rng_key(C.seed, (uint32_t)(C.env_offset + n), ctr);
   const V3<float> ef = v3<float>(B.applied_force[n * 3 + 0], B.applied_force[n * 3 + 1], B.applied_force[n * 3 + 2]);
   float vi_ft = B.contact_vimp[(size_t)n * NVIMP + vimp_foot(leg)];
-  int s_dof = 9 - B.dof_lag_timestep[n] % 10;
-#ifdef T1_MUTANT_CAPTURE  // mutation check of tests/test_gpu_product_parity.py only (tools/gpu): capture a substep early
-  s_dof = s_dof > 0 ? s_dof - 1 : 0;
-#endif
+  const int s_dof = 9 - B.dof_lag_timestep[n] % 10;
   const int s_imu = 9 - B.imu_lag_timestep[n] % 10;
   {  // actions = clip(actions) into the step's history slot, the PD constants and action ring staged
     PdStage<64>& P = lds.pd;
@@ -843,18 +786,6 @@ __global__ __launch_bounds__(D5_BLOCK) void k_dyn5(const DynModel* __restrict__ 
   }
   T1_PROF_END();
 }
-
-#ifdef T1_PHASE_PROF
-// profiling build only: summed clock deltas per [wave][bucket] since the last reset
-extern "C" int t1env_debug_phase_cycles5(unsigned long long* out, int reset) {
-  hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_t1_prof5), sizeof(g_t1_prof5));
-  if (e == hipSuccess && reset) {
-    static const unsigned long long zero[T1_PROF_WAVES5][T1_NPROF5] = {};
-    e = hipMemcpyToSymbol(HIP_SYMBOL(g_t1_prof5), zero, sizeof(zero));
-  }
-  return (int)e;
-}
-#endif
 
 int t1_launch_dyn5(const DynModel* d_model, const t1env_config* d_cfg, const t1env_buffers& B, const Terrain& T,
                    const float* actions, const t1env_step_args& A, int num_envs, const ShiftArgs& S,

@@ -25,7 +25,7 @@
 // approach of their points (amx), and W0 folds the two halves of a body into its episode after S2 (W4 keeps the base
 // box's, as k_dyn5's W1).  The history shift is not staged in LDS (the role hand-offs need it): each of the six shift
 // waves copies one tenth of its share of the workgroup's rows per substep through VGPRs, pipelined across the substep
-// -- slice s + 1's two aligned 16-B source loads per output chunk are issued right after slice s's stores and held in
+// -- slice s + 1's 16-B source load per output chunk is issued right after slice s's stores and held in
 // registers through the next substep's role work (ShiftHold), so the HBM stream spans the whole substep -- and stores
 // whole 16-B chunks (the newest frame of a row is a don't-care the epilogue rewrites; only the workgroup's last chunk
 // takes an element path).  The step's report and the fused epilogue are k_dyn5's, spread over the eight waves.
@@ -37,10 +37,8 @@
 
 // one inlined copy of the contact law per call site (body_contact_fixed_q, contact_half) instead of a copy
 // specialised for waves without a restitution set point: the -O2 build merged the two and indexed a scratch copy of
-// the query (-DT1_D6_VTG_SPECIALIZE: the two copies, A/B)
-#ifndef T1_D6_VTG_SPECIALIZE
+// the query
 #define T1_CONTACT_ONE_COPY
-#endif
 
 #ifdef T1_PROBE_SIMD
 // probe build only: the hardware placement of every wave of the last launch (HW_ID: SIMD, CU, SE), [block][wave]
@@ -90,52 +88,10 @@ __device__ unsigned long long g_t1_wgsum6[4096][3];
 #define T1_CLOCK_WAIT_END(k) ((void)0)
 #define T1_CLOCK_LOOP_END() ((void)0)
 #endif
-// -DT1_PHASE_PROF (tools/prof_dynamics_phases.py --kernel 6): lane 0 of every wave accumulates shader-clock deltas
-// between T1_PROF_MARK points into per-phase buckets; never part of the product build.
-#ifdef T1_PHASE_PROF
-constexpr int T1_NPROF6 = 24, T1_PROF_WAVES6 = 8;
-__device__ unsigned long long g_t1_prof6[T1_PROF_WAVES6][T1_NPROF6];
-__shared__ unsigned long long t1_prof_acc6[T1_PROF_WAVES6][T1_NPROF6 + 1];  // [wave][bucket], last = previous mark
-__device__ __forceinline__ unsigned long long t1_stamp6() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-__device__ __forceinline__ void t1_prof_mark6(int i) {
-  const int w = threadIdx.x / 64;
-  const unsigned long long now = t1_stamp6();
-  if ((threadIdx.x & 63) == 0) {
-    t1_prof_acc6[w][i] += now - t1_prof_acc6[w][T1_NPROF6];
-    t1_prof_acc6[w][T1_NPROF6] = now;
-  }
-}
-__device__ __forceinline__ void t1_prof_begin6() {
-  const int w = threadIdx.x / 64;
-  if ((threadIdx.x & 63) == 0) {
-    for (int i = 0; i < T1_NPROF6; ++i) t1_prof_acc6[w][i] = 0;
-    t1_prof_acc6[w][T1_NPROF6] = t1_stamp6();
-  }
-}
-__device__ __forceinline__ void t1_prof_end6() {
-  const int w = threadIdx.x / 64;
-  if ((threadIdx.x & 63) == 0)
-    for (int i = 0; i < T1_NPROF6; ++i) atomicAdd(&g_t1_prof6[w][i], t1_prof_acc6[w][i]);
-}
-#define T1_PROF_MARK(i) t1_prof_mark6(i)
-#define T1_PROF_BEGIN() t1_prof_begin6()
-#define T1_PROF_END() t1_prof_end6()
-#elif defined(T1_ASM_MARKS)  // ISA analysis build (tools/isa_phases.py): the marks as assembly comments
-#define T1_ASM_STR2(x) #x
-#define T1_ASM_STR(x) T1_ASM_STR2(x)
-#define T1_PROF_MARK(i) asm volatile(";@@MARK " #i "@L" T1_ASM_STR(__LINE__))
-#define T1_PROF_BEGIN() asm volatile(";@@MARK begin")
-#define T1_PROF_END() asm volatile(";@@MARK end")
-#else
-#define T1_PROF_BEGIN() ((void)0)
-#define T1_PROF_END() ((void)0)
-#endif
+
+#define T1_PROF_WAVES 8
+#define T1_PROF_NAME(x) x##6
+#include "t1env_prof.h"  // T1_PROF_MARK / _BEGIN / _END (tools/prof_dynamics_phases.py --kernel 6, tools/isa_phases.py)
 
 #include "t1_dyn5.h"
 #include "t1env_device.h"
@@ -157,31 +113,12 @@ struct SubspaceRows { float4 r[NLEG][2][64]; };  // S_k = (r[k][0], r[k][1].xy)
 enum : int { R_RG = 0, R_G = 6, R_N = 12 };
 // contact terms -> W0
 enum : int { WC_SHA = 0, WC_SHB = 1, WC_FTA = 2, WC_FTB = 3, WC_SSH = 4, WC_SFT = 5, WC_N = 6 };
-// the shift waves (post-S2) and their count
-#ifndef T1_D6_SHIFT_MASK  // A/B builds: -DT1_D6_SHIFT_MASK=...
-#define T1_D6_SHIFT_MASK ((1 << 1) | (1 << 5) | (1 << 2) | (1 << 6) | (1 << 3) | (1 << 7))
-#endif
-constexpr int SHIFT6_MASK = T1_D6_SHIFT_MASK;  // by role (below)
-// the shift roles that commit their slice (and issue the next one's loads) before S2, in the slack their role work
-// leaves ahead of the core wave's pre-S2 chain, instead of after S2 where the core wave may wait for them at S1
-// (-DT1_D6_SHIFT_PRE_MASK=..., by role; 0: every shift role after S2)
-#ifndef T1_D6_SHIFT_PRE_MASK
-#define T1_D6_SHIFT_PRE_MASK 0
-#endif
-constexpr int SHIFT6_PRE_MASK = T1_D6_SHIFT_PRE_MASK;
-// The role of each wave: role ids are the wave numbers of the table at the top (0 core, 4 base, 1 RNEA, 5 self, 2 / 6
-// shank halves, 3 / 7 foot halves); T1_D6_ROLE_MAP holds the role of wave w in hex digit w, so the SIMD pairs (w, w + 4)
-// can be re-dealt for A/B (the core stays wave 0: its partner is wave 4's role)
-#ifndef T1_D6_ROLE_MAP
-#define T1_D6_ROLE_MAP 0x76543210u
-#endif
-__device__ __forceinline__ int role_of(int wave) {
-#ifdef T1_PROBE_ROLE  // register-probe builds only (every wave one role: the others' code compiled out)
-  return T1_PROBE_ROLE;
-#endif
-  return (int)((T1_D6_ROLE_MAP >> (4 * wave)) & 0xFu);
-}
-static_assert((T1_D6_ROLE_MAP & 0xFu) == 0, "the core role is wave 0");
+// the shift waves (post-S2), by role, and their count
+constexpr int SHIFT6_MASK = (1 << 1) | (1 << 5) | (1 << 2) | (1 << 6) | (1 << 3) | (1 << 7);
+// The role of a wave is its wave number in the table at the top (0 core, 4 base, 1 RNEA, 5 self, 2 / 6 shank halves,
+// 3 / 7 foot halves).  The identity is spelled as a nibble look-up on purpose: with `role = wave` the compiler lays the
+// role dispatch out differently and the scratch frames of the two height-field kernels grow (8 -> 24 B, 16 -> 20 B).
+__device__ __forceinline__ int role_of(int wave) { return (int)((0x76543210u >> (4 * wave)) & 0xFu); }
 constexpr int SHIFT6_WAVES = __builtin_popcount(SHIFT6_MASK);
 static_assert((SHIFT6_MASK & 0x11) == 0, "W0 / W4 (the core chain's SIMD) do not shift");
 
@@ -200,7 +137,6 @@ struct Dyn6Lds {
   float vish[64];         // the shank's restitution episode (W0 updates it after S2; W2 / W6 read it)
   float vift[64];         // the foot's (W0; W3 / W7)
   float amx[4][64];       // the fastest approach among the points of the shank halves [0, 1] and foot halves [2, 3]
-  int s1flag;             // T1_D6_S1_FLAG: the number of substep states W0 has published (S1 as a one-way signal)
   LegParams<float> pl[64];   // W0's per-lane leg parameters (CRBA) and base parameters (report, log): LDS, not
   BaseParams<float> pb[64];  // registers held across the substep loop
   float rtf[2][3][64];    // the report: terrain forces on the shank [0] (W2) / foot [1] (W3)
@@ -210,22 +146,9 @@ struct Dyn6Lds {
 // ---- the history shift through VGPRs.  Output element e of a row-major history (rows of ROW = F * H) is input element
 // e + F unless e is in the row's newest frame (column >= ROW - F), which the epilogue (or k_post_b) of the same
 // workgroup writes after the shift has completed.  So a 16-B output chunk is stored whole -- its newest-frame elements
-// are don't-cares -- whenever it lies inside the workgroup's rows and its two aligned 16-B source blocks inside the
-// buffer; only a chunk crossing into the next workgroup's first row (whose epilogue may zero it for a reset: the race
-// the whole-chunk store must not enter) or sourcing past the buffer's end takes the element path.
-// bytes [OFF, OFF + 16) of the 32-B window a:b
-template <uint32_t OFF>
-__device__ __forceinline__ u32x4 shift_window(const float4& a, const float4& b) {
-  const u32x4 xa = __builtin_bit_cast(u32x4, a), xb = __builtin_bit_cast(u32x4, b);
-  const uint32_t w[8] = {xa.x, xa.y, xa.z, xa.w, xb.x, xb.y, xb.z, xb.w};
-  constexpr uint32_t M = OFF / 4, R = OFF % 4;
-  if constexpr (R == 0) {
-    return u32x4{w[M], w[M + 1], w[M + 2], w[M + 3]};
-  } else {
-    return u32x4{__builtin_amdgcn_alignbyte(w[M + 1], w[M], R), __builtin_amdgcn_alignbyte(w[M + 2], w[M + 1], R),
-                 __builtin_amdgcn_alignbyte(w[M + 3], w[M + 2], R), __builtin_amdgcn_alignbyte(w[M + 4], w[M + 3], R)};
-  }
-}
+// are don't-cares -- whenever it lies inside the workgroup's rows and its 16-B source inside the buffer; only a chunk
+// crossing into the next workgroup's first row (whose epilogue may zero it for a reset: the race the whole-chunk store
+// must not enter) or sourcing past the buffer's end takes the element path.
 // the element path of one chunk (elements [i, i + PER) of the workgroup's nel): older-frame columns only
 template <int F, int H, bool HALF>
 __device__ __forceinline__ void shift_chunk_elems(const uint8_t* in0, uint8_t* out0, uint32_t i, uint32_t nel) {
@@ -256,60 +179,36 @@ __device__ __forceinline__ void shp_range(int64_t total, int64_t r0, int64_t r1,
 }
 // One 16-B load from the exact source of a chunk (4-byte aligned for fp32 histories, 2-byte for fp16) -- the hardware
 // serves an unaligned dwordx4 (the unaligned access mode ROCm sets for gfx9; tools/probes/unaligned_x4.hip) -- instead
-// of the two aligned blocks around it and an alignbyte window (-DT1_D6_SHIFT_ALIGNED2, A/B): half the load instructions
-// of a slice and half the registers held across the substep (ShiftHold::b unused)
-#ifndef T1_D6_SHIFT_ALIGNED2
-constexpr bool SHIFT_EXACT32 = true;
-#else
-constexpr bool SHIFT_EXACT32 = false;
-#endif
-typedef float shift_f4 __attribute__((ext_vector_type(4)));
+// of the two aligned blocks around it and an alignbyte window: half the load instructions of a slice and half the
+// registers held across the substep.  The type states the alignment the address really has.
+typedef float shift_f4 __attribute__((ext_vector_type(4), aligned(2)));
 // the source loads of U chunks (lane t0's, `stride` apart from chunk lo)
 template <int F, bool HALF, int U>
 __device__ __forceinline__ void shift_loads(const uint8_t* in0, uint32_t lo, uint32_t lim, int t0, int stride,
-                                            float4* a, float4* b) {
+                                            float4* a) {
   constexpr uint32_t PER = HALF ? 8 : 4, ES = HALF ? 2 : 4;
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    const uint32_t c = lo + (uint32_t)(t0 + u * stride);
-    if constexpr (SHIFT_EXACT32) {
-      const uint32_t src = c * PER + F;
-      const uint32_t sc = src + PER <= lim ? src : lim - PER;  // tail: an in-bounds dummy
-      const shift_f4 v = *reinterpret_cast<const shift_f4*>(in0 + (size_t)sc * ES);
-      a[u] = make_float4(v.x, v.y, v.z, v.w);
-    } else {
-      const uint32_t sa = (c * PER + F) & ~(PER - 1);
-      const uint32_t sc = sa + 2 * PER <= lim ? sa : (lim - 2 * PER) & ~(PER - 1);  // tail: an aligned in-bounds dummy
-      a[u] = *reinterpret_cast<const float4*>(in0 + (size_t)sc * ES);
-      b[u] = *reinterpret_cast<const float4*>(in0 + (size_t)(sc + PER) * ES);
-    }
+    const uint32_t src = (lo + (uint32_t)(t0 + u * stride)) * PER + F;
+    const uint32_t sc = src + PER <= lim ? src : lim - PER;  // tail: an in-bounds dummy
+    const shift_f4 v = *reinterpret_cast<const shift_f4*>(in0 + (size_t)sc * ES);
+    a[u] = make_float4(v.x, v.y, v.z, v.w);
   }
 }
-// the stores of U chunks from their loaded source blocks (whole chunks; the rest by the element path)
+// the stores of U chunks from their loaded sources (whole chunks; the rest by the element path)
 template <int F, int H, bool HALF, int U>
 __device__ __forceinline__ void shift_stores(const uint8_t* in0, uint8_t* out0, uint32_t lo, uint32_t hi,
-                                             uint32_t lim, uint32_t nel, int t0, int stride, const float4* a,
-                                             const float4* b) {
-  constexpr uint32_t PER = HALF ? 8 : 4, ES = HALF ? 2 : 4, OFF = (F * ES) % 16;
+                                             uint32_t lim, uint32_t nel, int t0, int stride, const float4* a) {
+  constexpr uint32_t PER = HALF ? 8 : 4, ES = HALF ? 2 : 4;
   uint32_t slow = 0;
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const uint32_t c = lo + (uint32_t)(t0 + u * stride), i = c * PER;
-    if constexpr (SHIFT_EXACT32) {
-      if (c < hi) {
-        if (i + PER <= nel && i + F + PER <= lim)
-          __builtin_nontemporal_store(__builtin_bit_cast(u32x4, a[u]), reinterpret_cast<u32x4*>(out0 + (size_t)i * ES));
-        else
-          slow |= 1u << u;
-      }
-    } else {
-      const uint32_t sa = (i + F) & ~(PER - 1);
-      if (c < hi) {
-        if (i + PER <= nel && sa + 2 * PER <= lim)
-          __builtin_nontemporal_store(shift_window<OFF>(a[u], b[u]), reinterpret_cast<u32x4*>(out0 + (size_t)i * ES));
-        else
-          slow |= 1u << u;
-      }
+    if (c < hi) {
+      if (i + PER <= nel && i + F + PER <= lim)
+        __builtin_nontemporal_store(__builtin_bit_cast(u32x4, a[u]), reinterpret_cast<u32x4*>(out0 + (size_t)i * ES));
+      else
+        slow |= 1u << u;
     }
   }
   if (slow) {
@@ -323,9 +222,9 @@ template <int F, int H, bool HALF, int U>
 __device__ __forceinline__ void shift6_range(const uint8_t* in0, uint8_t* out0, uint32_t c_lo, uint32_t c_hi,
                                              uint32_t lim, uint32_t nel, int t0, int stride) {
   for (uint32_t base = c_lo; base + (uint32_t)t0 < c_hi; base += U * (uint32_t)stride) {
-    float4 a[U], b[U];
-    shift_loads<F, HALF, U>(in0, base, lim, t0, stride, a, b);
-    shift_stores<F, H, HALF, U>(in0, out0, base, c_hi, lim, nel, t0, stride, a, b);
+    float4 a[U];
+    shift_loads<F, HALF, U>(in0, base, lim, t0, stride, a);
+    shift_stores<F, H, HALF, U>(in0, out0, base, c_hi, lim, nel, t0, stride, a);
   }
 }
 // ---- the shift pipelined across the substep: a shift wave issues the source loads of slice s + 1 right after it
@@ -335,25 +234,25 @@ __device__ __forceinline__ void shift6_range(const uint8_t* in0, uint8_t* out0, 
 // with more chunks (fewer than 10 substeps) does the rest through shift6_f32 / _f16 at commit time.
 constexpr int SHP_UO = 7, SHP_UP = 1;  // 32 rows / 10 slices / (6 x 64) lanes: 6.5 actor chunks, 0.5 critic
 struct ShiftHold {
-  float4 a[SHP_UO + SHP_UP], b[SHP_UO + SHP_UP];  // the two aligned 16-B source blocks of each held chunk
+  float4 a[SHP_UO + SHP_UP];  // the 16-B source of each held chunk
 };
 template <int F, int H, bool HALF, int U>
 __device__ __forceinline__ void shp_issue(const void* in, int64_t total, int64_t r0, int64_t r1, int sl, int nsl,
-                                          int t0, int stride, float4* a, float4* b) {
+                                          int t0, int stride, float4* a) {
   constexpr uint32_t ROW = F * H, ES = HALF ? 2 : 4;
   uint32_t lo, hi, lim, nel;
   shp_range<F, H, HALF>(total, r0, r1, sl, nsl, lo, hi, lim, nel);
-  shift_loads<F, HALF, U>(reinterpret_cast<const uint8_t*>(in) + (size_t)(r0 * ROW) * ES, lo, lim, t0, stride, a, b);
+  shift_loads<F, HALF, U>(reinterpret_cast<const uint8_t*>(in) + (size_t)(r0 * ROW) * ES, lo, lim, t0, stride, a);
 }
 template <int F, int H, bool HALF, int U>
 __device__ __forceinline__ void shp_commit(const void* in, void* out, int64_t total, int64_t r0, int64_t r1, int sl,
-                                           int nsl, int t0, int stride, const float4* a, const float4* b) {
+                                           int nsl, int t0, int stride, const float4* a) {
   constexpr uint32_t ROW = F * H, ES = HALF ? 2 : 4;
   uint32_t lo, hi, lim, nel;
   shp_range<F, H, HALF>(total, r0, r1, sl, nsl, lo, hi, lim, nel);
   const uint8_t* in0 = reinterpret_cast<const uint8_t*>(in) + (size_t)(r0 * ROW) * ES;
   uint8_t* out0 = reinterpret_cast<uint8_t*>(out) + (size_t)(r0 * ROW) * ES;
-  shift_stores<F, H, HALF, U>(in0, out0, lo, hi, lim, nel, t0, stride, a, b);
+  shift_stores<F, H, HALF, U>(in0, out0, lo, hi, lim, nel, t0, stride, a);
   // chunks past the held ones (a slice larger than the lanes hold: fewer than 10 substeps)
   const uint32_t rest = lo + (uint32_t)(U * stride);
   if (rest < hi) shift6_range<F, H, HALF, 1>(in0, out0, rest, hi, lim, nel, t0, stride);
@@ -361,40 +260,37 @@ __device__ __forceinline__ void shp_commit(const void* in, void* out, int64_t to
 // issue slice sl's loads into H (shift wave wi); commit slice sl from H
 __device__ __forceinline__ void shp_issue_slice(const ShiftArgs& S, int64_t r0, int64_t r1, int sl, int nsl, int wi,
                                                 int lane, ShiftHold& Hd) {
-#ifdef T1_WHATIF_D6_NO_SHIFT
-  return;
-#endif
   if (r1 <= r0 || sl >= nsl) return;
   const int t0 = wi * 64 + lane, stride = 64 * SHIFT6_WAVES;
   if (S.half) {
-    shp_issue<T1_NOBS, T1_HIST, true, SHP_UO>(S.obs_in, S.total_obs, r0, r1, sl, nsl, t0, stride, Hd.a, Hd.b);
-    shp_issue<T1_NPRIV, T1_CHIST, true, SHP_UP>(S.priv_in, S.total_priv, r0, r1, sl, nsl, t0, stride, Hd.a + SHP_UO,
-                                                Hd.b + SHP_UO);
+    shp_issue<T1_NOBS, T1_HIST, true, SHP_UO>(S.obs_in, S.total_obs, r0, r1, sl, nsl, t0, stride, Hd.a);
+    shp_issue<T1_NPRIV, T1_CHIST, true, SHP_UP>(S.priv_in, S.total_priv, r0, r1, sl, nsl, t0, stride, Hd.a + SHP_UO);
   } else {
-    shp_issue<T1_NOBS, T1_HIST, false, SHP_UO>(S.obs_in, S.total_obs, r0, r1, sl, nsl, t0, stride, Hd.a, Hd.b);
-    shp_issue<T1_NPRIV, T1_CHIST, false, SHP_UP>(S.priv_in, S.total_priv, r0, r1, sl, nsl, t0, stride, Hd.a + SHP_UO,
-                                                 Hd.b + SHP_UO);
+    shp_issue<T1_NOBS, T1_HIST, false, SHP_UO>(S.obs_in, S.total_obs, r0, r1, sl, nsl, t0, stride, Hd.a);
+    shp_issue<T1_NPRIV, T1_CHIST, false, SHP_UP>(S.priv_in, S.total_priv, r0, r1, sl, nsl, t0, stride, Hd.a + SHP_UO);
   }
 }
 __device__ __forceinline__ void shp_commit_slice(const ShiftArgs& S, int64_t r0, int64_t r1, int sl, int nsl, int wi,
                                                  int lane, const ShiftHold& Hd) {
-#ifdef T1_WHATIF_D6_NO_SHIFT
-  return;
-#endif
   if (r1 <= r0 || sl >= nsl) return;
   const int t0 = wi * 64 + lane, stride = 64 * SHIFT6_WAVES;
-  const ShiftHold& H = Hd;
   if (S.half) {
-    shp_commit<T1_NOBS, T1_HIST, true, SHP_UO>(S.obs_in, S.obs_out, S.total_obs, r0, r1, sl, nsl, t0, stride, H.a,
-                                               H.b);
+    shp_commit<T1_NOBS, T1_HIST, true, SHP_UO>(S.obs_in, S.obs_out, S.total_obs, r0, r1, sl, nsl, t0, stride, Hd.a);
     shp_commit<T1_NPRIV, T1_CHIST, true, SHP_UP>(S.priv_in, S.priv_out, S.total_priv, r0, r1, sl, nsl, t0, stride,
-                                                 H.a + SHP_UO, H.b + SHP_UO);
+                                                 Hd.a + SHP_UO);
   } else {
-    shp_commit<T1_NOBS, T1_HIST, false, SHP_UO>(S.obs_in, S.obs_out, S.total_obs, r0, r1, sl, nsl, t0, stride, H.a,
-                                                H.b);
+    shp_commit<T1_NOBS, T1_HIST, false, SHP_UO>(S.obs_in, S.obs_out, S.total_obs, r0, r1, sl, nsl, t0, stride, Hd.a);
     shp_commit<T1_NPRIV, T1_CHIST, false, SHP_UP>(S.priv_in, S.priv_out, S.total_priv, r0, r1, sl, nsl, t0, stride,
-                                                  H.a + SHP_UO, H.b + SHP_UO);
+                                                  Hd.a + SHP_UO);
   }
+}
+// a shift role's tail of substep `sub`, after S2: commit slice `sub` (its loads issued a substep ago), then issue
+// slice `sub + 1`'s loads (wi: shift6_index of the role)
+__device__ __forceinline__ void shp_step(const ShiftArgs& S, int64_t r0, int64_t r1, int sub, int nsub, int wi,
+                                         int lane, ShiftHold& Hd) {
+  if (wi < 0) return;
+  shp_commit_slice(S, r0, r1, sub, nsub, wi, lane, Hd);
+  shp_issue_slice(S, r0, r1, sub + 1, nsub, wi, lane, Hd);
 }
 
 __device__ __forceinline__ int shift6_index(int role) {  // the role's index among the shifting roles, -1: none
@@ -410,28 +306,6 @@ __device__ __forceinline__ const DynModel& model_in_loop(const DynModel& m) {
   asm volatile("" : "+s"(p));
   return *(const DynModel*)p;
 }
-
-// S1 as a one-way signal (-DT1_D6_S1_FLAG): W0 publishes the substep state and counts it in an LDS word instead of
-// meeting the other seven waves at a workgroup barrier, so it starts its next pre-S2 chain at once; a role wave waits
-// for the count before it reads the state.  What S1 also ordered still holds: W0 finishes its reads of the role rows
-// (wb, w1, wc, amx) before it publishes, and the role waves write them only after the count, and S2 (a full barrier)
-// keeps W0 from publishing over a state a role still reads.  The wait is bounded (it never runs long: W0 signals
-// every substep), so a fault cannot turn into a hang.
-__device__ __forceinline__ void s1_signal(int* flag, int value) {
-  __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void s1_wait(int* flag, int target) {
-  for (int i = 0; i < (1 << 22); ++i) {
-    const int v = __builtin_amdgcn_readfirstlane(__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-    if (v >= target) break;
-    __builtin_amdgcn_s_sleep(1);
-  }
-}
-#ifdef T1_D6_S1_FLAG
-#define D6_S1(target) s1_wait(&lds.s1flag, (target))
-#else
-#define D6_S1(target) __syncthreads()
-#endif
 
 // the other leg's capsule ends and velocity (from the other half of the wave) for the self-contact terms / forces
 __device__ __forceinline__ void self_bodies(const DynModel& M, int leg, const BodyKin<float> (&Ko)[2],
@@ -469,12 +343,7 @@ __device__ __forceinline__ void contact_half(const DynModel& M, const Terrain& T
     const int32_t bnd = terrain_bound_raw_any(T, K.p.x + F.abs.x, K.p.y + F.abs.y);
     if (K.p.z + F.abs.z - M.contact_radius[b] > bound_height<float>(T, bnd)) return;
   }
-#ifdef T1_D6_VTG_SPECIALIZE  // A/B: the contact law specialised for a wave without a restitution set point
-  if (t1_wave_any(vtg > 0.0f)) contact_apply<HF, T1_POINTS_PER_BODY / 2>(M, Q, K.V, mu, vtg, dt, C, c, amax);
-  else contact_apply<HF, T1_POINTS_PER_BODY / 2>(M, Q, K.V, mu, 0.0f, dt, C, c, amax);
-#else  // one copy of the contact law (the -O2 build merged the two and indexed a scratch copy of Q)
   contact_apply<HF, T1_POINTS_PER_BODY / 2>(M, Q, K.V, mu, vtg, dt, C, c, amax);
-#endif
 }
 
 // leg_apply_terms (t1_dyn5.h) with its inputs read from LDS where they are used, to hold the core wave's register peak:
@@ -619,7 +488,6 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
   const int nsub = C.decimation;
   const int64_t r0 = (int64_t)blockIdx.x * NE6, r1 = r0 + NE6 < N ? r0 + NE6 : N;
   T1_PROF_BEGIN();
-  if (threadIdx.x == 0) lds.s1flag = 0;
   __syncthreads();  // the model in LDS
   const DynModel& M = lds.model;
 
@@ -629,17 +497,6 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
                                                  // the loop); read from the first substep on
     // the friction and restitution, lag, force and episode loads, then the actions and PD constants below, before the
     // first global store (the buffers may alias as far as the compiler knows)
-#ifdef T1_D6_STAGE_FIRST  // A/B: the staging loads first (0.1275 vs 0.1270 ms, r05st: not kept)
-    EpiStage<NE6, 256> EV;
-    if (FUSED) epi_stage_load<NE6, 256>(B, N, (int)r0, (int)threadIdx.x - 256, EV);
-#endif
-#ifdef T1_PROBE_SCRATCH  // probe build only: a 64-B per-lane scratch object, touched once in W4's prologue
-    {
-      volatile float pad[16];
-      pad[lane & 15] = 1.0f;
-      if (pad[(lane + 3) & 15] == 12345.0f) B.torques[0] = 0.0f;
-    }
-#endif
     const float mu = 0.5f * (B.friction[n] + M.ground_friction);  // load_base_params' friction, restitution
     const float eg = ground_restitution(M, B.restitution[n]);
     const int lag = B.lag_timestep[n];
@@ -679,16 +536,12 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
     }
     // the epilogue's inputs the step does not change, staged by W4-W7 before their first substep (staged by W4 alone
     // in the first substep's idle S2 -> S1 window instead: 0.1301 vs 0.1269 ms, its loop's registers spill, r05stage)
-#ifdef T1_D6_STAGE_FIRST
-    if (FUSED) epi_stage_store<NE6, 256>(N, (int)r0, (int)threadIdx.x - 256, EV, lds.epi);
-#else
     if (FUSED) stage_epilogue_inputs<NE6, 256>(B, N, (int)r0, (int)threadIdx.x - 256, lds.epi);
-#endif
     int cb, ce;
     base_contact_range(M, leg, cb, ce);
     T1_PROF_MARK(0);
     for (int sub = 0; sub < nsub; ++sub) {
-      D6_S1(sub + 1);  // S1: the substep state published
+      __syncthreads();  // S1: the substep state published
       T1_PROF_MARK(1);
       const DynModel& M = model_in_loop(lds.model);
       BaseState<float> sb;
@@ -803,7 +656,7 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
       if (wi >= 0) shp_issue_slice(S, r0, r1, 0, nsub, wi, lane, hold);
       for (int sub = 0; sub < nsub; ++sub) {
         T1_PROF_MARK(4);
-        D6_S1(sub + 1);  // S1
+        __syncthreads();  // S1
         T1_PROF_MARK(1);
         BaseState<float> sb;
         float q[NLEG], qd[NLEG];
@@ -818,17 +671,10 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
 #pragma unroll
         for (int i = 0; i < 6; ++i) v[R_G + i] = G[i];
         put4(lds.w1, lane, v);
-        if (wi >= 0 && ((SHIFT6_PRE_MASK >> role) & 1)) {  // the slice before S2 (T1_D6_SHIFT_PRE_MASK)
-          shp_commit_slice(S, r0, r1, sub, nsub, wi, lane, hold);
-          shp_issue_slice(S, r0, r1, sub + 1, nsub, wi, lane, hold);
-        }
         T1_PROF_MARK(2);
         __syncthreads();  // S2
         T1_PROF_MARK(3);
-        if (wi >= 0 && !((SHIFT6_PRE_MASK >> role) & 1)) {  // slice sub (its loads issued a substep ago), then
-          shp_commit_slice(S, r0, r1, sub, nsub, wi, lane, hold);  // slice sub + 1's loads
-          shp_issue_slice(S, r0, r1, sub + 1, nsub, wi, lane, hold);
-        }
+        shp_step(S, r0, r1, sub, nsub, wi, lane, hold);
       }
     } else if (role == 5) {
       // ---- W5: self-contact terms of the shank and foot
@@ -836,7 +682,7 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
       if (wi >= 0) shp_issue_slice(S, r0, r1, 0, nsub, wi, lane, hold);
       for (int sub = 0; sub < nsub; ++sub) {
         T1_PROF_MARK(4);
-        D6_S1(sub + 1);  // S1
+        __syncthreads();  // S1
         T1_PROF_MARK(1);
         BaseState<float> sb;
         float q[NLEG], qd[NLEG];
@@ -864,26 +710,16 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
           sym_pack(Cs[i], cs[i], v);
           put4(lds.wc[WC_SSH + i], lane, v);
         }
-        if (wi >= 0 && ((SHIFT6_PRE_MASK >> role) & 1)) {  // the slice before S2 (T1_D6_SHIFT_PRE_MASK)
-          shp_commit_slice(S, r0, r1, sub, nsub, wi, lane, hold);
-          shp_issue_slice(S, r0, r1, sub + 1, nsub, wi, lane, hold);
-        }
         T1_PROF_MARK(2);
         __syncthreads();  // S2
         T1_PROF_MARK(3);
-        if (wi >= 0 && !((SHIFT6_PRE_MASK >> role) & 1)) {  // slice sub (its loads issued a substep ago), then
-          shp_commit_slice(S, r0, r1, sub, nsub, wi, lane, hold);  // slice sub + 1's loads
-          shp_issue_slice(S, r0, r1, sub + 1, nsub, wi, lane, hold);
-        }
+        shp_step(S, r0, r1, sub, nsub, wi, lane, hold);
       }
     } else {
       // ---- W2 / W6: shank terrain, W3 / W7: foot terrain (one half of the body's points each); W6 also records the
       // sensor-lag samples and the substep log from the state it reads at S1
       const bool shank = role == 2 || role == 6;
-      int s_dof = 9 - B.dof_lag_timestep[n] % 10;
-#ifdef T1_MUTANT_CAPTURE  // mutation check of tests/test_gpu_product_parity.py only (tools/gpu): capture a substep early
-      s_dof = s_dof > 0 ? s_dof - 1 : 0;
-#endif
+      const int s_dof = 9 - B.dof_lag_timestep[n] % 10;
       const int s_imu = 9 - B.imu_lag_timestep[n] % 10;
 
       const int slot = (shank ? WC_SHA : WC_FTA) + half;
@@ -893,7 +729,7 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
       if (wi >= 0) shp_issue_slice(S, r0, r1, 0, nsub, wi, lane, hold);
       for (int sub = 0; sub < nsub; ++sub) {
         T1_PROF_MARK(4);
-        D6_S1(sub + 1);  // S1
+        __syncthreads();  // S1
         T1_PROF_MARK(1);
         BaseState<float> sb;
         float q[NLEG], qd[NLEG];
@@ -919,17 +755,10 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
         sym_pack(Cc, cc, v);
         put4(lds.wc[slot], lane, v);
         lds.amx[slot][lane] = amax;
-        if (wi >= 0 && ((SHIFT6_PRE_MASK >> role) & 1)) {  // the slice before S2 (T1_D6_SHIFT_PRE_MASK)
-          shp_commit_slice(S, r0, r1, sub, nsub, wi, lane, hold);
-          shp_issue_slice(S, r0, r1, sub + 1, nsub, wi, lane, hold);
-        }
         T1_PROF_MARK(2);
         __syncthreads();  // S2
         T1_PROF_MARK(3);
-        if (wi >= 0 && !((SHIFT6_PRE_MASK >> role) & 1)) {  // slice sub (its loads issued a substep ago), then
-          shp_commit_slice(S, r0, r1, sub, nsub, wi, lane, hold);  // slice sub + 1's loads
-          shp_issue_slice(S, r0, r1, sub + 1, nsub, wi, lane, hold);
-        }
+        shp_step(S, r0, r1, sub, nsub, wi, lane, hold);
       }
     }
     T1_PROF_MARK(4);
@@ -968,10 +797,7 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
       }
       T1_PROF_MARK(10);
       if (role == 6) {  // the last substep's state (published before R1): its log row, then the lag samples' stores
-        int s_dof = 9 - B.dof_lag_timestep[n] % 10;
-#ifdef T1_MUTANT_CAPTURE
-        s_dof = s_dof > 0 ? s_dof - 1 : 0;
-#endif
+        const int s_dof = 9 - B.dof_lag_timestep[n] % 10;
         const int s_imu = 9 - B.imu_lag_timestep[n] % 10;
         BaseState<float> sb;
         float q[NLEG], qd[NLEG];
@@ -1015,11 +841,7 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
     if constexpr (FUSED) {
       __syncthreads();  // the epilogue barrier: every output of the workgroup is in LDS / memory
       T1_PROF_MARK(12);
-#ifndef T1_WHATIF_D6_EPI_SKIP  // timing-only what-if builds: bit r set = role r skips its epilogue part
-#define T1_WHATIF_D6_EPI_SKIP 0
-#endif
-      if ((T1_WHATIF_D6_EPI_SKIP >> role) & 1) {
-      } else if (role == 1)
+      if (role == 1)
         fused_epilogue_staged<POST_A_STATE, NE6, true>(M, C, B, A, S, FA, dyn_blocks, lane, lds.epi, lds.fr, lds.act,
                                                        lds.act + NLEG);
       else if (role == 2)
@@ -1061,42 +883,30 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
   lds.vift[lane] = vi_ft;
   lds.vish[lane] = vi_sh;
   T1_PROF_MARK(0);
-#ifdef T1_D6_S1_FLAG
-  s1_signal(&lds.s1flag, 1);  // the first substep's state (and the episodes) published
-#endif
   for (int sub = 0; sub < nsub; ++sub) {
-#ifndef T1_D6_S1_FLAG
     {
       T1_CLOCK_WAIT_BEGIN();
       __syncthreads();  // S1: the substep state published
       T1_CLOCK_WAIT_END(1);
     }
-#endif
     T1_PROF_MARK(1);
-    // -DT1_D6_LAUNDER (A/B): the lane and leg through an empty asm each substep, so the lane- and leg-indexed LDS
-    // addresses are formed in the loop instead of hoisted and spilled: no scratch reloads in the loop, yet measured
-    // 0.5-1% slower (r05ab2, r05o2)
-    int lane_s = lane, leg_s = leg;
-#ifdef T1_D6_LAUNDER
-    asm volatile("" : "+v"(lane_s), "+v"(leg_s));
-#endif
     const DynModel& M = model_in_loop(lds.model);
     LegBlock<float> lb;
     Sym6<float> Ab;
     {
       BaseState<float> sb;
       float q[NLEG], qd[NLEG];
-      read_state_rows(lds.st, lane_s, sb, q, qd);
+      read_state_rows(lds.st, lane, sb, q, qd);
       const M3<float> R0 = quat_to_mat(sb.quat[0], sb.quat[1], sb.quat[2], sb.quat[3]);  // base_frame's F.R0
       LegFK<float> fk;
-      leg_fk_chain(M, R0, q, leg_s, fk);
+      leg_fk_chain(M, R0, q, leg, fk);
       float Sj[NLEG][6];
       sym_zero(Ab);
-      leg_backward_crba(M, PL, q, qd, leg_s, dt, fk, Sj, lb, Ab);
+      leg_backward_crba(M, PL, q, qd, leg, dt, fk, Sj, lb, Ab);
 #pragma unroll
       for (int k = 0; k < NLEG; ++k) {  // the joint subspaces to LDS for the fold-in (registers at its peak)
-        lds.sj.r[k][0][lane_s] = make_float4(Sj[k][0], Sj[k][1], Sj[k][2], Sj[k][3]);
-        lds.sj.r[k][1][lane_s] = make_float4(Sj[k][4], Sj[k][5], 0.0f, 0.0f);
+        lds.sj.r[k][0][lane] = make_float4(Sj[k][0], Sj[k][1], Sj[k][2], Sj[k][3]);
+        lds.sj.r[k][1][lane] = make_float4(Sj[k][4], Sj[k][5], 0.0f, 0.0f);
       }
     }
     T1_PROF_MARK(2);
@@ -1107,25 +917,21 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
     }
     T1_PROF_MARK(3);
     {  // the episodes of the shank and foot from the two halves of their points
-      vi_sh = restitution_episode(vi_sh, fmaxf(lds.amx[WC_SHA][lane_s], lds.amx[WC_SHB][lane_s]));
-      vi_ft = restitution_episode(vi_ft, fmaxf(lds.amx[WC_FTA][lane_s], lds.amx[WC_FTB][lane_s]));
-      lds.vish[lane_s] = vi_sh;  // W2 / W6 read it after the next S1
-      lds.vift[lane_s] = vi_ft;  // W3 / W7
+      vi_sh = restitution_episode(vi_sh, fmaxf(lds.amx[WC_SHA][lane], lds.amx[WC_SHB][lane]));
+      vi_ft = restitution_episode(vi_ft, fmaxf(lds.amx[WC_FTA][lane], lds.amx[WC_FTB][lane]));
+      lds.vish[lane] = vi_sh;  // W2 / W6 read it after the next S1
+      lds.vift[lane] = vi_ft;  // W3 / W7
     }
     float g6[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     {
       float rg[NLEG];  // dt tau_k (W4's torques, the first two rows of wb) + the bias part (W1)
-      const float4 t0 = lds.wb.r[0][lane_s], t1 = lds.wb.r[1][lane_s];
-      const float4 g0 = lds.w1.r[0][lane_s], g1 = lds.w1.r[1][lane_s];
+      const float4 t0 = lds.wb.r[0][lane], t1 = lds.wb.r[1][lane];
+      const float4 g0 = lds.w1.r[0][lane], g1 = lds.w1.r[1][lane];
       const float tv[NLEG] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y}, gv[NLEG] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y};
       static_assert(WB_TAU == 0 && R_RG == 0, "the torques and the bias rhs lead their rows");
 #pragma unroll
       for (int k = 0; k < NLEG; ++k) rg[k] = dt * tv[k] + gv[k];
-#ifndef T1_WHATIF_D6_NO_FOLDIN  // timing-only what-if build: the contact / bias terms not folded in
-      leg_apply_terms_rows<K_SHANK, K_FOOT>(lds.wc, lds.w1, rg, lds.sj, lane_s, lb, Ab, g6);
-#else
-      for (int k = 0; k < NLEG; ++k) lb.rhs[k] += rg[k];
-#endif
+      leg_apply_terms_rows<K_SHANK, K_FOOT>(lds.wc, lds.w1, rg, lds.sj, lane, lb, Ab, g6);
     }
     T1_PROF_MARK(5);
     float rb[6];
@@ -1138,7 +944,7 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
     float r[6];
     {
       float v[WB_N];
-      get4(lds.wb, lane_s, v);
+      get4(lds.wb, lane, v);
 #pragma unroll
       for (int i = 0; i < 21; ++i) Ac.a[i] = v[WB_AC + i];
 #pragma unroll
@@ -1161,15 +967,12 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
     backsub_leg(lb, r, dq);
     BaseState<float> sb;
     float q[NLEG], qd[NLEG];
-    read_state_rows(lds.st, lane_s, sb, q, qd);
+    read_state_rows(lds.st, lane, sb, q, qd);
     integrate_base(sb, r, dt);
-    integrate_leg(M, leg_s, q, qd, dq, dt);
+    integrate_leg(M, leg, q, qd, dq, dt);
     float v[Q_N];
     state_pack(sb, q, qd, v);
-    put4(lds.st, lane_s, v);  // the roles read the previous state before S2; after the last substep: the report's
-#ifdef T1_D6_S1_FLAG
-    s1_signal(&lds.s1flag, sub + 2);
-#endif
+    put4(lds.st, lane, v);  // the roles read the previous state before S2; after the last substep: the report's
     T1_PROF_MARK(7);
   }
   T1_CLOCK_LOOP_END();
@@ -1239,18 +1042,6 @@ extern "C" int t1env_debug_clock6(unsigned long long* out, int reset) {
   if (e == hipSuccess && reset) {
     static const unsigned long long zero[4] = {};
     e = hipMemcpyToSymbol(HIP_SYMBOL(g_t1_clock6), zero, sizeof(zero));
-  }
-  return (int)e;
-}
-#endif
-
-#ifdef T1_PHASE_PROF
-// profiling build only: summed clock deltas per [wave][bucket] since the last reset
-extern "C" int t1env_debug_phase_cycles6(unsigned long long* out, int reset) {
-  hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_t1_prof6), sizeof(g_t1_prof6));
-  if (e == hipSuccess && reset) {
-    static const unsigned long long zero[T1_PROF_WAVES6][T1_NPROF6] = {};
-    e = hipMemcpyToSymbol(HIP_SYMBOL(g_t1_prof6), zero, sizeof(zero));
   }
   return (int)e;
 }

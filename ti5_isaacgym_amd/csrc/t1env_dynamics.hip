@@ -4,48 +4,9 @@
 // correct too (tests/test_gpu_opt_levels.py runs the -O3 build through the fp64 dynamics check and the product replay).
 #include <hip/hip_runtime.h>
 
-// -DT1_PHASE_PROF (tools/prof_dynamics_phases.py): lane 0 of every dynamics wave accumulates shader-clock
-// deltas between T1_PROF_MARK points into per-phase buckets; never part of the product build.
-#ifdef T1_PHASE_PROF
-constexpr int T1_NPROF = 24, T1_PROF_WAVES = 4;
-__device__ unsigned long long g_t1_prof[T1_PROF_WAVES][T1_NPROF];
-__shared__ unsigned long long t1_prof_acc[T1_PROF_WAVES][T1_NPROF + 1];  // [wave][bucket], last = previous mark
-// a stamp is one asm statement (s_memtime + its lgkmcnt wait) fenced by scheduling barriers, so the compiler
-// cannot move work across it (cdna_hip_programming.md, In-kernel stamps); profiling build only
-__device__ __forceinline__ unsigned long long t1_stamp() {
-  unsigned long long t;
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  return t;
-}
-__device__ __forceinline__ void t1_prof_mark(int i) {
-  const int w = threadIdx.x / 64;
-  const unsigned long long now = t1_stamp();
-  if ((threadIdx.x & 63) == 0) {
-    t1_prof_acc[w][i] += now - t1_prof_acc[w][T1_NPROF];
-    t1_prof_acc[w][T1_NPROF] = now;
-  }
-}
-__device__ __forceinline__ void t1_prof_begin() {
-  const int w = threadIdx.x / 64;
-  if ((threadIdx.x & 63) == 0) {
-    for (int i = 0; i < T1_NPROF; ++i) t1_prof_acc[w][i] = 0;
-    t1_prof_acc[w][T1_NPROF] = t1_stamp();
-  }
-}
-__device__ __forceinline__ void t1_prof_end() {
-  const int w = threadIdx.x / 64;
-  if ((threadIdx.x & 63) == 0)
-    for (int i = 0; i < T1_NPROF; ++i) atomicAdd(&g_t1_prof[w][i], t1_prof_acc[w][i]);
-}
-#define T1_PROF_MARK(i) t1_prof_mark(i)
-#define T1_PROF_BEGIN() t1_prof_begin()
-#define T1_PROF_END() t1_prof_end()
-#else
-#define T1_PROF_BEGIN() ((void)0)
-#define T1_PROF_END() ((void)0)
-#endif
+#define T1_PROF_WAVES 4
+#define T1_PROF_NAME(x) x
+#include "t1env_prof.h"  // T1_PROF_MARK / _BEGIN / _END (tools/prof_dynamics_phases.py --kernel 4)
 
 #include "t1env_device.h"
 #include "t1env_internal.h"
@@ -95,9 +56,7 @@ constexpr int DYN_ENVS = 64;
 constexpr int D4_BLOCK = 4 * DYN_ENVS;
 // chunks per lane in flight in the in-launch shift: the shift workgroups run one wave per SIMD on the CUs the dynamics
 // leave idle, so they need deep per-lane batches (r02u: 8 -> 16 took the shift alone from 114 to 106 us at 8192 envs)
-#ifndef T1_FUSED_SHIFT_UNROLL
-#define T1_FUSED_SHIFT_UNROLL 16
-#endif
+constexpr int T1_FUSED_SHIFT_UNROLL = 16;
 static_assert(DYN_ENVS % SHIFT_UNIT == 0, "a dynamics workgroup owns whole shift units");
 
 // A history-shift workgroup (j of nsw) of BS threads; `words` is LDS scratch of >= BS uint32.
@@ -118,12 +77,10 @@ __device__ __forceinline__ void shift_workgroup(const ShiftArgs& S, const FusedA
     const int per = (units + nsw - 1) / nsw;
     const int u0 = j * per < units ? j * per : units, u1 = u0 + per < units ? u0 + per : units;
     const int mine = u1 - u0;  // units of this workgroup
-#ifndef T1_WHATIF_NO_SHIFT  // timing-only what-if build: the history is not shifted (handoff and zeroing kept)
     if (mine > 0) {
       const int64_t r0 = (int64_t)u0 * SHIFT_UNIT, r1 = (int64_t)u1 * SHIFT_UNIT < N ? (int64_t)u1 * SHIFT_UNIT : N;
       shift_rows_range_sc1<T1_FUSED_SHIFT_UNROLL>(S, r0, r1, threadIdx.x, BS);
     }
-#endif
     // every lane's sc1 stores complete (visible at agent scope) before any handoff
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
@@ -215,11 +172,6 @@ __device__ __forceinline__ void body_terms_at(const DynModel& M, const Terrain& 
 // of the leg's pose region, written after integration, read by the helpers between S1 and S2 (and after R1).
 enum : int { ST_POS = 0, ST_QUAT = 3, ST_W = 7, ST_VO = 10, ST_Q = 13, ST_QD = 19, ST_N = 25 };
 static_assert(ST_N <= POSE_N, "the substep state fits the pose rows");
-#ifdef T1_WHATIF_NO_SELF  // timing-only what-if build: the self-collision code compiled out of k_dyn4
-#define T1_SELF_CODE 0
-#else
-#define T1_SELF_CODE 1
-#endif
 // a helper's kinematics of one published state: the base frame and the contact bodies of leg `leg` (own state P)
 __device__ __forceinline__ void helper_kinematics(const DynModel& M, const float (*P)[DYN_ENVS], int lane, int leg,
                                                   BaseFrame<float>& F, BodyKin<float> (&Ko)[2]) {
@@ -297,12 +249,7 @@ __device__ __forceinline__ void exchange_self_bodies(const DynModel& M, Dyn4Lds&
 // parameter: the logged and the product step are the same code object, so the log cannot change the arithmetic
 // (r03: a separate LOG instantiation differed from the product's by up to 2.5e-5 in obs, compiler contraction).
 template <bool HF, bool FUSED>
-#ifdef T1_DYN4_WAVES_PER_EU1  // A/B: tell the scheduler one wave per SIMD is the target (it is, by registers)
-#define T1_DYN4_ATTR __attribute__((amdgpu_waves_per_eu(1, 1)))
-#else
-#define T1_DYN4_ATTR
-#endif
-__global__ __launch_bounds__(D4_BLOCK) T1_DYN4_ATTR void k_dyn4(const DynModel* __restrict__ Mp, const t1env_config* __restrict__ Cp,
+__global__ __launch_bounds__(D4_BLOCK) void k_dyn4(const DynModel* __restrict__ Mp, const t1env_config* __restrict__ Cp,
                                                    t1env_buffers B, Terrain Tin, const float* __restrict__ actions,
                                                    t1env_step_args A, ShiftArgs S, int dyn_blocks, FusedArgs FA,
                                                    SubLog LG, int shift_delay) {
@@ -351,7 +298,7 @@ __global__ __launch_bounds__(D4_BLOCK) T1_DYN4_ATTR void k_dyn4(const DynModel* 
       BodyKin<float> Ko[2];
       helper_kinematics(M, P, lane, leg, F, Ko);
       SelfBody<float> Os[2], Xs[2];
-      if (T1_SELF_CODE && M.self_collisions) exchange_self_bodies(M, lds, lane, leg, sub + 1, Ko, Os, Xs);
+      if (M.self_collisions) exchange_self_bodies(M, lds, lane, leg, sub + 1, Ko, Os, Xs);
       T1_PROF_MARK(20);
       const V3<float> abs = F.abs;
       const int32_t bound_base = terrain_bound_raw_any(T, abs.x, abs.y);
@@ -366,7 +313,7 @@ __global__ __launch_bounds__(D4_BLOCK) T1_DYN4_ATTR void k_dyn4(const DynModel* 
       // the foot's terrain queries go out first; the self-contact terms run while its height loads are in flight
       body_contact_query_apply<T1_POINTS_PER_BODY>(M, T, M.contact_start[1 + 6 * leg + K_FOOT], Ko[1].Rb, Ko[1].p, abs,
                                                    Ko[1].V, mu, e, vi_ft, dt, Cs[1], cs[1], [&] {
-        if (T1_SELF_CODE && M.self_collisions) self_terms_bodies(M, leg, Os, Xs, mu_self, dt, Cs, cs);
+        if (M.self_collisions) self_terms_bodies(M, leg, Os, Xs, mu_self, dt, Cs, cs);
         T1_PROF_MARK(21);
       });
       lds_put_sym(lds.ct[leg] + XCH, lane, Cs[1], cs[1]);
@@ -399,7 +346,7 @@ __global__ __launch_bounds__(D4_BLOCK) T1_DYN4_ATTR void k_dyn4(const DynModel* 
       BodyKin<float> Ko[2];
       helper_kinematics(M, P, lane, leg, F, Ko);
       V3<float> fself[2] = {v3<float>(0.0f, 0.0f, 0.0f), v3<float>(0.0f, 0.0f, 0.0f)};
-      if (T1_SELF_CODE && M.self_collisions) {
+      if (M.self_collisions) {
         SelfBody<float> Os[2], Xs[2];
         exchange_self_bodies(M, lds, lane, leg, C.decimation + 1, Ko, Os, Xs);
         self_forces_bodies(M, leg, Os, Xs, mu_self, fself);
@@ -502,19 +449,6 @@ __global__ __launch_bounds__(D4_BLOCK) T1_DYN4_ATTR void k_dyn4(const DynModel* 
       }
       lds_get_sym(lds.ct[leg] + XCH, lane, Cft, cft);
       leg_apply_contacts<K_SHANK, K_FOOT>(Csh, csh, Cft, cft, tau, dt, st, lb, Ab, g6);
-#ifdef T1_WHATIF_FOLD2  // timing-only: the fold-in and elimination run twice (second result scaled by 0 and added)
-      {
-        LegBlock<float> lb2 = lb;
-        Sym6<float> Ab2 = Ab;
-        float g2[6], rb2[6];
-        for (int i = 0; i < 6; ++i) g2[i] = g6[i];
-        leg_apply_contacts<K_SHANK, K_FOOT>(Csh, csh, Cft, cft, tau, dt, st, lb2, Ab2, g2);
-        for (int i = 0; i < 6; ++i) rb2[i] = -g2[i];
-        eliminate_leg(lb2, Ab2, rb2);
-        for (int i = 0; i < 21; ++i) Ab.a[i] += 0.0f * Ab2.a[i];
-        for (int i = 0; i < 6; ++i) g6[i] += 0.0f * rb2[i];
-      }
-#endif
     }
     float rb[6];
 #pragma unroll
@@ -537,11 +471,7 @@ __global__ __launch_bounds__(D4_BLOCK) T1_DYN4_ATTR void k_dyn4(const DynModel* 
     integrate_base(sb, r, dt);
     integrate_leg(M, leg, q, qd, dq, dt);
     T1_PROF_MARK(9);
-#ifdef T1_WHATIF_NO_LOG  // timing-only what-if build: the substep-log branch compiled out
-    if (false) {
-#else
     if (LG.root != nullptr) {  // wave-uniform (a kernel argument)
-#endif
       if (active) {
         const size_t row = (size_t)sub * N + n;
 #pragma unroll
@@ -627,13 +557,13 @@ __global__ __launch_bounds__(D4_BLOCK) T1_DYN4_ATTR void k_dyn4(const DynModel* 
 // 0.247 vs 0.268 ms, 32768 hf + push 0.485 vs 0.519), but not with fp16 histories, where k_dyn4's stand-alone shift
 // launch halves and k_dyn4's 64 envs per workgroup are the better throughput (r05cfg5: 32768 hf + push 0.437 vs 0.471,
 // 16384 0.216 vs 0.240).  T1ENV_DYN_KERNEL=4|5|6 overrides (A/B).
-int t1_dyn_waves_default(int num_envs, int cus, bool obs_half) {
+int t1_dyn_kernel_default(int num_envs, int cus, bool obs_half) {
   return obs_half && (num_envs + 31) / 32 > cus ? 4 : 6;
 }
 
 constexpr int MIN_SHIFT_BLOCKS = 64;
 bool t1_shift_prelaunch(int num_envs, const DynLaunch& cfg) {
-  if (cfg.waves >= 5) return false;        // k_dyn5 / k_dyn6: every workgroup shifts its own rows
+  if (cfg.kernel >= 5) return false;        // k_dyn5 / k_dyn6: every workgroup shifts its own rows
   if (cfg.shift_blocks < 0) return true;   // forced stand-alone shift (tuning: T1ENV_SHIFT_BLOCKS=-1)
   if (cfg.shift_blocks > 0) return false;  // explicit shift-workgroup count (tuning)
   const int dyn_blocks = (num_envs + DYN_ENVS - 1) / DYN_ENVS;
@@ -644,8 +574,8 @@ int t1_launch_dynamics(const DynModel* d_model, const t1env_config* d_cfg, const
                        const float* actions, const t1env_step_args& A, int num_envs, const ShiftArgs& S,
                        const DynLaunch& cfg, const FusedArgs* fused, hipStream_t s, bool shift_prelaunched,
                        const SubLog* log) {
-  if (cfg.waves == 6) return t1_launch_dyn6(d_model, d_cfg, B, T, actions, A, num_envs, S, fused, s, log);
-  if (cfg.waves == 5)  // the shift in the workgroup (d5_shift 0) or the caller's concurrent k_shift5 launch (1)
+  if (cfg.kernel == 6) return t1_launch_dyn6(d_model, d_cfg, B, T, actions, A, num_envs, S, fused, s, log);
+  if (cfg.kernel == 5)  // the shift in the workgroup (d5_shift 0) or the caller's concurrent k_shift5 launch (1)
     return t1_launch_dyn5(d_model, d_cfg, B, T, actions, A, num_envs, S, fused, s, log, cfg.d5_shift == 0);
   const int dyn_blocks = (num_envs + DYN_ENVS - 1) / DYN_ENVS;
   // history-shift workgroups: the workgroup slots the dynamics leave free (a k_dyn4 wave holds a whole SIMD's
@@ -669,15 +599,3 @@ int t1_launch_dynamics(const DynModel* d_model, const t1env_config* d_cfg, const
 #undef T1_LAUNCH
   return (int)hipGetLastError();
 }
-
-#ifdef T1_PHASE_PROF
-// profiling build only: summed clock deltas per [wave][bucket] since the last reset
-extern "C" int t1env_debug_phase_cycles(unsigned long long* out, int reset) {
-  hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_t1_prof), sizeof(g_t1_prof));
-  if (e == hipSuccess && reset) {
-    static const unsigned long long zero[T1_PROF_WAVES][T1_NPROF] = {};
-    e = hipMemcpyToSymbol(HIP_SYMBOL(g_t1_prof), zero, sizeof(zero));
-  }
-  return (int)e;
-}
-#endif

@@ -81,9 +81,6 @@ __device__ __forceinline__ void epilogue_handoff(const t1env_config& C, const Sh
 __device__ __forceinline__ void epilogue_finalize_parts(const t1env_config& C, const t1env_buffers& B,
                                                         const t1env_step_args& A, const FusedArgs& FA, int dyn_blocks,
                                                         int lane) {
-#ifdef T1_WHATIF_NO_FINALIZE  // timing-only what-if build: no completion counter, no extras
-  return;
-#endif
   unsigned prev = 0;
   // Ordering: the increment is RELAXED and no release fence precedes it.  What orders the ep_part rows
   // before it is gfx950 hardware behaviour, not the HIP memory model: every row element is a relaxed agent-scope
@@ -163,9 +160,6 @@ __device__ __forceinline__ LegSetup leg_setup(const DynModel& M, const t1env_con
   LegSetup L;
   L.lag = B.lag_timestep[n];
   L.s_dof = 9 - B.dof_lag_timestep[n] % 10;
-#ifdef T1_MUTANT_CAPTURE  // mutation check of tests/test_gpu_product_parity.py only (tools/gpu): capture a substep early
-  L.s_dof = L.s_dof > 0 ? L.s_dof - 1 : 0;
-#endif
   L.s_imu = 9 - B.imu_lag_timestep[n] % 10;
   L.dof_dst = B.dof_hist + ((size_t)n * 4 + (ctr & 3u)) * 24;
   L.imu_dst = B.imu_hist + ((size_t)n * 2 + (ctr & 1u)) * 8;
@@ -356,14 +350,7 @@ __device__ __forceinline__ void fused_epilogue_staged(const DynModel& M, const t
   X.gstart = E[E_GS][e];
   BaseQ bq;
   float* const ep_row = FA.ep_part + (size_t)blockIdx.x * EP_PART_ROW;  // this workgroup's partial extras sums
-#ifdef T1_WHATIF_EPI_NO_POSTA  // timing-only what-if build: no post_a (no rewards, termination, callback)
-  const bool do_reset = false;
-  base_quantities_r(X.root, bq);
-  if (PART == POST_A_REWARDS && lane < 25)  // the finaliser still sums every row (agent-scope stores, as wave_sum_store)
-    __hip_atomic_store(ep_row + lane, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
   const bool do_reset = post_a_core<PART>(M, C, B, A, n0, X, bq, PART == POST_A_REWARDS ? ep_row : nullptr);
-#endif
   T1_PROF_MARK(13);
   if constexpr (PART == POST_A_REWARDS) {
     epilogue_handoff<NE, INWG>(C, S, FA, lane, do_reset, active);

@@ -34,9 +34,9 @@ constexpr int T1_SHIFT_DELAY_DEFAULT = 3000;
 
 // launch shape of the dynamics kernel
 struct DynLaunch {
-  int waves;         // 6: k_dyn6 (t1env_dyn6.hip: 32 envs per workgroup, eight role waves, two per SIMD), 5: k_dyn5
+  int kernel;        // 6: k_dyn6 (t1env_dyn6.hip: 32 envs per workgroup, eight role waves, two per SIMD), 5: k_dyn5
                      //    (t1env_dyn5.hip: 32 envs per workgroup, four roles, in-workgroup history shift), 4: k_dyn4
-                     //    (64 envs per workgroup, leg + contact helper waves); t1_dyn_waves_default picks k_dyn6
+                     //    (64 envs per workgroup, leg + contact helper waves); t1_dyn_kernel_default picks k_dyn6
                      //    (k_dyn4 for fp16 histories above one round), T1ENV_DYN_KERNEL=4|5|6 overrides
   int cus;           // compute units of the device (default history-shift grid)
   int shift_blocks;  // > 0: history-shift workgroups override (tuning)
@@ -47,7 +47,7 @@ struct DynLaunch {
                      // concurrent launch on a second stream beside the dynamics (k_shift4c, the default), 0 = its own
                      // launch ahead of them in stream order (T1ENV_D4_SHIFT=0, A/B)
 };
-int t1_dyn_waves_default(int num_envs, int cus, bool obs_half);
+int t1_dyn_kernel_default(int num_envs, int cus, bool obs_half);
 
 // dynamics launch (t1env_dynamics.hip) plus history-shift workgroups running the shift S; fused != nullptr:
 // the whole step (post-physics in the epilogue).  shift_prelaunched: the caller already enqueued the shift as

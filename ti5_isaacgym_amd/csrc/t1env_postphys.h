@@ -701,14 +701,12 @@ __device__ __forceinline__ void reset_env(const DynModel& M, const t1env_config&
         rand_float(C.armature_range[j][0], C.armature_range[j][1], K, SLOT_DR_ARMATURE + j);
   }
   // randomize_lag_props: zero the lag rings, redraw lag lengths
-#ifndef T1_WHATIF_NO_RING_ZERO  // timing-only what-if build
 #pragma unroll
   for (int i = 0; i < 48; ++i) B.act_hist[(size_t)n * 48 + i] = 0.0f;
 #pragma unroll
   for (int i = 0; i < 96; ++i) B.dof_hist[(size_t)n * 96 + i] = 0.0f;
 #pragma unroll
   for (int i = 0; i < 16; ++i) B.imu_hist[(size_t)n * 16 + i] = 0.0f;
-#endif
   B.lag_timestep[n] = rand_int(C.lag_range[0], C.lag_range[1] + 1, K, SLOT_LAG_ACTION);
   B.dof_lag_timestep[n] = R.dl;
   B.imu_lag_timestep[n] = R.il;
@@ -902,11 +900,7 @@ __device__ __forceinline__ void store_actor_frame(const DynModel& M, const t1env
   for (int i = 0; i < 3; ++i) v[k++] = li[3 + i] * C.quat_obs_scale;
 #pragma unroll
   for (int i = 0; i < T1_NOBS; ++i) {
-#ifdef T1_WHATIF_NO_NOISE_DRAWS  // timing-only what-if build
-    const float nz = 0.0f;
-#else
     const float nz = obs_noise(C, K, i);
-#endif
     v[i] = clampf(v[i] + nz, -clipo, clipo);
   }
   if (C.obs_half) {
@@ -933,18 +927,8 @@ __device__ __forceinline__ void load_lagged(const t1env_buffers& B, const t1env_
                                             float (&ld)[24], float (&lraw)[8]) {
   const float* ldp = B.dof_hist + ((size_t)n * 4 + ((A.counter - (uint32_t)(dl / 10)) & 3u)) * 24;
   const float* lip = B.imu_hist + ((size_t)n * 2 + ((A.counter - (uint32_t)(il / 10)) & 1u)) * 8;
-#ifdef T1_WHATIF_NO_LAG_LOADS  // timing-only what-if build: the lagged sensor samples not loaded
-  (void)ldp;
-  (void)lip;
-#pragma unroll
-  for (int i = 0; i < 24; ++i) ld[i] = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) lraw[i] = 0.0f;
-  lraw[3] = 1.0f;
-#else
   ldrow(ld, ldp);
   ldrow(lraw, lip);
-#endif
 }
 
 // X: the inputs as they stand after post_a (reloaded here after a reset)
