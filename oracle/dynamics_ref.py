@@ -108,7 +108,9 @@ class Robot:
 # same discrete law densely from plain kinematics:
 #   * point Jacobians J_x (velocity of a body-fixed point w.r.t. u = [omega, v_O, qd]) by central differences of
 #     forward kinematics -- no spatial algebra shared with the product;
-#   * terrain: the plane z = 0 (normal +z), contact candidates = the model's contact points below it;
+#   * terrain: the plane z = 0 (normal +z), contact candidates = the model's contact points below it; or, with a
+#     MeshTerrain, the triangle mesh of a height field: a point is in contact when it is below the triangle over / under
+#     it (h - z > 0), the depth is (h - z) n_z along that triangle's unit normal n;
 #   * self-collision: the legs' capsules (utils/urdf.py self_capsules: left shank, left foot, right shank, right foot);
 #     per overlapping pair one contact at the middle of the overlap along the segments' closest points (found here by
 #     enumerating the 2-parameter problem's interior stationary point and its four edges; near-parallel segments,
@@ -163,11 +165,56 @@ def _closest_segments(p1, q1, p2, q2):
     return p1 + sv * d1, p2 + tv * d2
 
 
+class MeshTerrain:
+    """A height field as the explicit triangle mesh the reference's trimesh construction makes of it (without its
+    slope-threshold correction, which the product leaves out too): vertex (i, j) at (i hs - border, j hs - border,
+    vs h[i, j]), rows along x, and per cell the two triangles on either side of the diagonal (i, j)-(i+1, j+1).
+
+    Queries work on the mesh alone: the triangle containing (x, y) by a 2-D barycentric test over all triangles, the
+    height by barycentric interpolation of its vertices, the normal from the cross product of its edges."""
+
+    def __init__(self, heights, hs, vs, border):
+        h = np.asarray(heights)
+        rows, cols = h.shape
+        ii, jj = np.meshgrid(np.arange(rows), np.arange(cols), indexing="ij")
+        self.vertices = np.stack([ii * float(hs) - float(border), jj * float(hs) - float(border),
+                                  float(vs) * h.astype(np.float64)], -1).reshape(-1, 3)
+        tris, half = [], []
+        for i in range(rows - 1):
+            for j in range(cols - 1):
+                v00, v01, v10, v11 = i * cols + j, i * cols + j + 1, (i + 1) * cols + j, (i + 1) * cols + j + 1
+                tris += [(v00, v11, v01), (v00, v10, v11)]
+                half += [0, 1]          # 0: the triangle with the cell's (i, j+1) corner, 1: the one with (i+1, j)
+        self.triangles = np.array(tris)
+        self.half = np.array(half)
+        a, b, c = (self.vertices[self.triangles[:, k]] for k in range(3))
+        self._a, self._ab, self._ac = a, b - a, c - a
+        self._det = self._ab[:, 0] * self._ac[:, 1] - self._ab[:, 1] * self._ac[:, 0]
+        n = np.cross(self._ab, self._ac)
+        n *= np.sign(n[:, 2:3])                                      # upward
+        self.normals = n / np.linalg.norm(n, axis=1, keepdims=True)
+
+    def query(self, x, y):
+        """(height, unit normal, barycentric margin, half) of the triangle over / under (x, y); the margin is the
+        smallest barycentric coordinate (0 on an edge of the triangle)"""
+        dx, dy = x - self._a[:, 0], y - self._a[:, 1]
+        l1 = (dx * self._ac[:, 1] - dy * self._ac[:, 0]) / self._det
+        l2 = (dy * self._ab[:, 0] - dx * self._ab[:, 1]) / self._det
+        l0 = 1.0 - l1 - l2
+        margin = np.minimum(l0, np.minimum(l1, l2))
+        t = int(np.argmax(margin))
+        if margin[t] < 0:
+            raise ValueError(f"({x}, {y}) is outside the height field")
+        h = self._a[t, 2] + l1[t] * self._ab[t, 2] + l2[t] * self._ac[t, 2]
+        return float(h), self.normals[t].copy(), float(margin[t]), int(self.half[t])
+
+
 class ContactRobot(Robot):
     def __init__(self, tab, mass=None, inertia_scale=None, com_disp=(0, 0, 0), armature=None, solver=None,
-                 limits=None):
+                 limits=None, terrain=None):
         super().__init__(tab, mass, inertia_scale, com_disp, armature)
         self.tab = tab
+        self.terrain = terrain               # a MeshTerrain, or None: the plane z = 0
         self.sv = dict(solver)
         lim = np.asarray(tab["limits"], float) if limits is None else np.asarray(limits, float)
         self.lo, self.hi = lim[:, 0], lim[:, 1]
@@ -186,6 +233,19 @@ class ContactRobot(Robot):
             J[:, k] = (self._points(Rp, pp, b, local) - self._points(Rm, pm, b, local)) / (2 * eps)
         return J
 
+    def terrain_points(self, p, R, q):
+        """every contact point of the robot against the mesh terrain: [(body, point index, world position, terrain
+        height h there, the triangle's normal, its barycentric margin, its half of the cell)]; in contact: h - z > 0"""
+        Rs, ps, _ = self.fk(p, R, q)
+        pts = np.asarray(self.tab["contact_point"], float)
+        out = []
+        for b in range(13):
+            s, n = self.tab["contact_start"][b], self.tab["contact_count"][b]
+            for c in range(s, s + n):
+                x = self._points(Rs, ps, b, pts[c])
+                out.append((b, c, x) + self.terrain.query(x[0], x[1]))
+        return out
+
     def contacts(self, p, R, q, u, mu_ground, e_ground, mu_self, e_self, self_collision=True):
         """[(body, local point, normal, pen, other body's point or None, mu, episode slot or None)] of the state;
         episode slots: 2 leg + (0 shank, 1 foot), 4 + leg for the base box half the point belongs to"""
@@ -196,8 +256,12 @@ class ContactRobot(Robot):
             s, n = self.tab["contact_start"][b], self.tab["contact_count"][b]
             for c in range(s, s + n):
                 x = self._points(Rs, ps, b, pts[c])
-                if x[2] < 0:
-                    slot = 4 + (c - s) * 2 // n if b == 0 else 2 * ((b - 1) // 6) + (1 if (b - 1) % 6 == 5 else 0)
+                slot = 4 + (c - s) * 2 // n if b == 0 else 2 * ((b - 1) // 6) + (1 if (b - 1) % 6 == 5 else 0)
+                if self.terrain is not None:
+                    h, nrm, _, _ = self.terrain.query(x[0], x[1])
+                    if h - x[2] > 0:
+                        out.append((b, pts[c], nrm, (h - x[2]) * nrm[2], None, mu_ground, slot))
+                elif x[2] < 0:
                     out.append((b, pts[c], np.array([0.0, 0.0, 1.0]), -x[2], None, mu_ground, slot))
         if self_collision:
             caps = _capsules(self.tab)

@@ -103,8 +103,9 @@ def _place_on_ground(robot, root, dof, rng, depth=(0.001, 0.004)):
         root[i, 2] = -zmin - rng.uniform(*depth)
 
 
-def host_du(setup, root, dof, tau, fr, rst, flags, dt=DT, vimp=None):
-    """the product header's substep (fp64 host build) -> du per env (and the restitution episodes after it)"""
+def host_du(setup, root, dof, tau, fr, rst, flags, dt=DT, vimp=None, terrain=None):
+    """the product header's substep (fp64 host build) -> du per env (and the restitution episodes after it);
+    terrain: (int16 heights (rows along x), hs, vs, border, mesh type 1 / 2), default the plane"""
     dyn, m, tab = setup
     n = root.shape[0]
     fp = C.POINTER(C.c_float)
@@ -117,13 +118,14 @@ def host_du(setup, root, dof, tau, fr, rst, flags, dt=DT, vimp=None):
     arm = np.full((n, 12), 0.1, np.float32)
     f32 = lambda a: np.ascontiguousarray(a, np.float32)  # noqa: E731
     t, fr, rst = f32(tau), f32(fr), f32(rst)
-    hf = np.zeros((2, 2), np.int16)
+    hf, hs, vs, border, mesh = (np.zeros((2, 2), np.int16), 0.1, 0.005, 0.0, 0) if terrain is None else terrain
+    hf = np.ascontiguousarray(hf, np.int16)
     vi = np.ascontiguousarray(np.zeros((n, 6)) if vimp is None else vimp, np.float32).copy()
     rc = dyn.t1dyn_substeps(C.byref(m), n, flags, r.ctypes.data_as(fp), d.ctypes.data_as(fp), t.ctypes.data_as(fp),
                             bm.ctypes.data_as(fp), ls.ctypes.data_as(fp), cd.ctypes.data_as(fp), arm.ctypes.data_as(fp),
                             fr.ctypes.data_as(fp), rst.ctypes.data_as(fp), vi.ctypes.data_as(fp), None, C.c_float(dt), 1,
-                            hf.ctypes.data_as(C.POINTER(C.c_int16)), 2, 2, C.c_float(0.1), C.c_float(0.005),
-                            C.c_float(0.0), 0, None, None)
+                            hf.ctypes.data_as(C.POINTER(C.c_int16)), hf.shape[0], hf.shape[1], C.c_float(hs), C.c_float(vs),
+                            C.c_float(border), mesh, None, None)
     assert rc == 0
     com0 = np.asarray(tab["com"], float)[0]
     out = []
@@ -138,13 +140,13 @@ def host_du(setup, root, dof, tau, fr, rst, flags, dt=DT, vimp=None):
     return np.array(out), r0, d0, vi
 
 
-def ref_du(setup, r0, d0, tau, fr, rst, dt=DT, count=None, vimp=None, episodes=None):
+def ref_du(setup, r0, d0, tau, fr, rst, dt=DT, count=None, vimp=None, episodes=None, terrain=None):
     from ti5_isaacgym_amd.envs.t1_env import SOLVER
     dyn, m, tab = setup
     com0 = np.asarray(tab["com"], float)[0]
     solver = dict(SOLVER, bounce_threshold=m.bounce_threshold)
     lim = np.array([[m.q_lower[j], m.q_upper[j]] for j in range(12)], float)
-    rob = ContactRobot(tab, armature=np.full(12, np.float32(0.1)), solver=solver, limits=lim)
+    rob = ContactRobot(tab, armature=np.full(12, np.float32(0.1)), solver=solver, limits=lim, terrain=terrain)
     out = []
     for i in range(r0.shape[0]):
         R0, w0 = quat_to_R(r0[i, 3:7]), r0[i, 10:13]
