@@ -144,7 +144,13 @@ int t1policy_linear_wgrad_f32(const float* gy, const float* x, int rows, int M, 
                               void* stream);
 
 /* t1policy_linear_wgrad_f32 with x's rows ldx >= N elements apart (a column slice read in place: the state estimator's
- * short history).  Returns 0, -1 on bad arguments (a strided x needs T1_WGRAD_STAGED on), -2 on a launch error. */
+ * short history).  Two kernels: the staged-split one (the default) addresses gy and x through 32-bit byte offsets and
+ * takes them only while rows * M * 4 and rows * ldx * 4 both lie below 2^30 (1 GiB per operand); from there on, or with
+ * T1_WGRAD_STAGED=0, the first-form kernel (64-bit indexing) runs, which reads a contiguous x only (ldx == N).
+ * Limits: rows * max(M, ldx) < 2^31 and M * N + M < 2^31.
+ * Returns 0, -1 on bad arguments, on a size past those limits, and on a strided x (ldx > N) that the staged kernel
+ * cannot take (an operand of 1 GiB or more, or T1_WGRAD_STAGED=0) -- dh_policy.linear_wgrad_f32 then copies x and
+ * calls t1policy_linear_wgrad_f32 --, -2 on a launch error. */
 int t1policy_linear_wgrad_f32x(const float* gy, const float* x, int ldx, int rows, int M, int N, void* workspace,
                                long long workspace_bytes, float* grad_weight, float* grad_bias, int accumulate,
                                void* stream);
@@ -155,7 +161,11 @@ int t1policy_linear_wgrad_f32x(const float* gy, const float* x, int ldx, int row
  * y = x W^T + b (B = W) and its input gradient gx = gy W (B = W^T) of every layer of actor_critic_dh.py:45-111 in the
  * update (dh_ppo.py:155-182; torch's addmm / mm before).  Each fp32 value split into three bf16 parts, the six part
  * products down to 2^-16 of each product on v_mfma_f32_32x32x16_bf16, fp32 sums in k order (fp32-class; deterministic).
- * Returns 0, -1 on bad arguments, -2 on a launch error. */
+ * Operands of any size up to R * max(K, N) < 2^31 elements: while A (R * K * 4 bytes) and B (N * K * 4 bytes) both lie
+ * below 2^30 (1 GiB) the staged-split kernel runs (t1policy_gemm_f32 below, 32-bit byte offsets); from there on, or
+ * with T1_GEMM_STAGED=0, the first-form kernel with 64-bit indexing -- the same parts, products and k order.
+ * Returns 0, -1 on bad arguments or R * max(K, N) >= 2^31 (dh_policy.gemm_nt_f32 then uses torch's addmm), -2 on a
+ * launch error. */
 int t1policy_gemm_nt_f32(const float* A, const float* B, const float* bias, const float* aux, float* C, int R, int N,
                          int K, int act, void* stream);
 
@@ -163,8 +173,10 @@ int t1policy_gemm_nt_f32(const float* A, const float* B, const float* bias, cons
  * elements apart (a column slice of a wider matrix: the state estimator's short history, obs[:, -235:]), and B either
  * (N, K) rows ldb >= K apart (b_kn = 0) or given as its transpose, (K, N) rows ldb >= N apart (b_kn = 1: the input
  * gradient gx = g W of a Linear reads its weight W (out, in) in place as B = W^T).  The same parts, products and k-order
- * sums as t1policy_gemm_nt_f32.  Each operand's extent below 1 GiB.  Returns 0, -1 on bad arguments, -2 on a launch
- * error. */
+ * sums as t1policy_gemm_nt_f32.  The staged-split kernel only (32-bit byte offsets, no first-form fallback here):
+ * R * lda * 4, (b_kn ? K : N) * ldb * 4 both below 2^30 (1 GiB per operand, strides included) and R * N < 2^31.
+ * Returns 0, -1 on bad arguments or an operand at or past those limits -- dh_policy.gemm_nt_f32 then copies A and B
+ * to contiguous tensors and calls t1policy_gemm_nt_f32, which has the fallback --, -2 on a launch error. */
 int t1policy_gemm_f32(const float* A, int lda, const float* B, int ldb, int b_kn, const float* bias, const float* aux,
                       float* C, int R, int N, int K, int act, void* stream);
 

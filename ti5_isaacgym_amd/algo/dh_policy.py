@@ -164,7 +164,11 @@ def linear_wgrad_f32(gy, x, need_bias=True, into=None):
     gy = gy.float().contiguous()
     x = x.float()
     if x.dim() == 2 and x.stride(1) == 1 and x.stride(0) > x.shape[1] and x.shape[0] > 1:  # a column slice, in place
-        return _linear_wgrad("t1policy_linear_wgrad_f32x", gy, x, need_bias, into, ldx=x.stride(0))
+        out = _linear_wgrad("t1policy_linear_wgrad_f32x", gy, x, need_bias, into, ldx=x.stride(0), may_refuse=True)
+        if out is not None:
+            return out
+        # refused (-1): only the staged kernel reads a strided x, and it takes operands below 1 GiB (rows * ldx * 4,
+        # rows * M * 4 < 2^30; T1_WGRAD_STAGED on) -- past that the slice is copied and the contiguous entry picks its kernel
     return _linear_wgrad("t1policy_linear_wgrad_f32", gy, x.contiguous(), need_bias, into)
 
 
@@ -195,33 +199,59 @@ def gemm_nt_f32(a, b, bias=None, act=0, aux=None):
         b = b.contiguous()
         b_kn, ldb = 0, K
     out = torch.empty(R, N, device=a.device, dtype=torch.float32)
+    if act not in (0, 1, 2):
+        raise ValueError(f"gemm_nt_f32: act {act}")
+    if act == 2 and (aux is None or tuple(aux.shape) != (R, N) or aux.dtype != torch.float32):
+        raise ValueError("gemm_nt_f32: act=2 needs the (R, N) fp32 ELU outputs")
+    if R == 0 or N == 0:   # an empty result, as torch's addmm / mm give
+        return out
     bp = xp = None
     if bias is not None:
         bias = bias.contiguous()
         bp = bias.data_ptr()
     if act == 2:
-        if aux is None or tuple(aux.shape) != (R, N) or aux.dtype != torch.float32:
-            raise ValueError("gemm_nt_f32: act=2 needs the (R, N) fp32 ELU outputs")
         aux = aux.contiguous()
         xp = aux.data_ptr()
     st = torch.cuda.current_stream(a.device).cuda_stream
     lda = a.stride(0)
-    if lda == K and ldb == K and not b_kn:
-        rc = lib.t1policy_gemm_nt_f32(a.data_ptr(), b.data_ptr(), bp, xp, out.data_ptr(), R, N, K, act, st)
-    else:
+    strided = not (lda == K and ldb == K and not b_kn)
+    rc = -1
+    if strided and K > 0:
         rc = lib.t1policy_gemm_f32(a.data_ptr(), lda, b.data_ptr(), ldb, b_kn, bp, xp, out.data_ptr(), R, N, K, act, st)
+        if rc == -1:
+            # refused: the in-place entry has the staged kernel only, whose 32-bit offsets take operands below 1 GiB
+            # (strides included) -- copy, and let the contiguous entry pick its kernel (the first form from 1 GiB on)
+            a, b = a.contiguous(), b.contiguous()
+    if rc == -1 and K > 0:
+        rc = lib.t1policy_gemm_nt_f32(a.data_ptr(), b.data_ptr(), bp, xp, out.data_ptr(), R, N, K, act, st)
+    if rc == -1 and (K == 0 or R * max(K, N) >= 2 ** 31):
+        # past the kernels' 2^31-element limit (or nothing to sum): torch's GEMM and the same epilogues in torch
+        a, b = a.contiguous(), b.contiguous()
+        y = torch.addmm(bias, a, b.t()) if bias is not None else a.mm(b.t())
+        if act == 1:
+            y = nn.functional.elu(y)
+        elif act == 2:
+            y = y * torch.where(aux > 0, torch.ones_like(aux), aux + 1.0)
+        return y
     if rc != 0:
         raise RuntimeError(f"t1policy_gemm_f32 failed (rc={rc}; R {R}, N {N}, K {K}, lda {lda}, ldb {ldb}, b_kn {b_kn})")
     return out
 
 
-def _linear_wgrad(fn, gy, x, need_bias, into, ldx=None):
+def _linear_wgrad(fn, gy, x, need_bias, into, ldx=None, may_refuse=False):
+    """may_refuse: None instead of a RuntimeError when the entry refuses the arguments (rc -1, before any launch: the
+    gradients of into= are untouched), for a caller with another way to the same sums."""
     from .. import _lib
     lib = _lib.load()
     K, M = gy.shape
     N = x.shape[1]
     if x.shape[0] != K:
         raise ValueError(f"{fn}: {K} gradient rows against {x.shape[0]} input rows")
+    if K == 0 or M == 0 or N == 0:   # empty sums: zero gradients, as torch's mm / sum give; into= stays as it is
+        if into is not None:
+            return into
+        return (torch.zeros(M, N, device=gy.device, dtype=torch.float32),
+                torch.zeros(M, device=gy.device, dtype=torch.float32) if need_bias else None)
     nbytes = lib.t1policy_linear_wgrad_workspace_bytes(K, M, N)
     if nbytes <= 0:
         raise RuntimeError(f"t1policy_linear_wgrad_workspace_bytes failed ({nbytes})")
@@ -239,6 +269,8 @@ def _linear_wgrad(fn, gy, x, need_bias, into, ldx=None):
     rc = getattr(lib, fn)(gy.data_ptr(), x.data_ptr(), *rows_args, ws.data_ptr(), nbytes, gw.data_ptr(),
                           gb.data_ptr() if gb is not None else None, int(into is not None),
                           torch.cuda.current_stream(gy.device).cuda_stream)
+    if rc == -1 and may_refuse:
+        return None
     if rc != 0:
         raise RuntimeError(f"{fn} failed (rc={rc})")
     return gw, gb
