@@ -30,6 +30,23 @@ def quat_to_R(q):
                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
+def R_to_quat(R):
+    """(x, y, z, w) of a rotation matrix (Shepperd: the branch with the largest of w^2, x^2, y^2, z^2)"""
+    t = np.array([R[0, 0] + R[1, 1] + R[2, 2], R[0, 0] - R[1, 1] - R[2, 2], R[1, 1] - R[0, 0] - R[2, 2],
+                  R[2, 2] - R[0, 0] - R[1, 1]])
+    i = int(np.argmax(t))
+    s = 2.0 * np.sqrt(1.0 + t[i])
+    if i == 0:
+        out = [(R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s, 0.25 * s]
+    elif i == 1:
+        out = [0.25 * s, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s, (R[2, 1] - R[1, 2]) / s]
+    elif i == 2:
+        out = [(R[0, 1] + R[1, 0]) / s, 0.25 * s, (R[1, 2] + R[2, 1]) / s, (R[0, 2] - R[2, 0]) / s]
+    else:
+        out = [(R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, 0.25 * s, (R[1, 0] - R[0, 1]) / s]
+    return np.array(out)
+
+
 class Robot:
     def __init__(self, tab, mass=None, inertia_scale=None, com_disp=(0, 0, 0), armature=None):
         self.parent = tab["parent"]
@@ -279,6 +296,116 @@ class ContactRobot(Robot):
                 la, lb = Rs[a].T @ (x - ps[a]), Rs[bb].T @ (x - ps[bb])
                 out.append((a, la, n, pen, (bb, lb), mu_self, None))
                 out.append((bb, lb, -n, pen, (a, la), mu_self, None))
+        return out
+
+    def velocities(self, p, R, q, u, points=(), eps=1e-6):
+        """(COM velocity (13, 3), angular velocity (13, 3), velocity of each (body, local point) of `points`) at
+        generalized speeds u: central differences of forward kinematics along the motion itself, J u as one
+        directional difference (x(+eps u) - x(-eps u)) / 2 eps instead of jacobians() / point_jacobian()'s 18 columns
+        times u (the same quantity to O(eps^2)); angular velocity from (R+ - R-) R^T / 2 eps, skew to O(eps^2)"""
+        Rs, _, _ = self.fk(p, R, q)
+        Rp, pp, cp = self.fk(*self._move(p, R, q, u, eps))
+        Rm, pm, cm = self.fk(*self._move(p, R, q, u, -eps))
+        vc = (np.array(cp) - np.array(cm)) / (2 * eps)
+        wb = np.zeros((13, 3))
+        for b in range(13):
+            W = (Rp[b] - Rm[b]) @ Rs[b].T / (2 * eps)
+            wb[b] = 0.5 * np.array([W[2, 1] - W[1, 2], W[0, 2] - W[2, 0], W[1, 0] - W[0, 1]])
+        vx = np.array([(self._points(Rp, pp, b, local) - self._points(Rm, pm, b, local)) / (2 * eps)
+                       for b, local in points]).reshape(len(points), 3)
+        return vc, wb, vx
+
+    def _target(self, e_ground, vimp):
+        return e_ground * vimp if vimp > self.sv["bounce_threshold"] else 0.0
+
+    def _contact_velocities(self, p, R, q, u, cons):
+        """velocity of each contact's point relative to the surface it touches (the terrain: at rest; a self-contact:
+        the other body's velocity at the same point)"""
+        pts = [(c[0], c[1]) for c in cons] + [c[4] for c in cons if c[4] is not None]
+        _, _, vx = self.velocities(p, R, q, u, pts)
+        out, nxt = [], len(cons)
+        for i, c in enumerate(cons):
+            vp = vx[i]
+            if c[4] is not None:
+                vp, nxt = vp - vx[nxt], nxt + 1
+            out.append(vp)
+        return out
+
+    def episodes_after(self, p, quat, w, v, q, qd, vimp, detail=None):
+        """the restitution episodes after a substep that starts at this state with episodes vimp -- step()'s rule (a
+        slot without a point in contact closes, an open one keeps its speed, a closed one opens at its fastest
+        approach) without its dense solve; detail (a list): (slot, v_n) of every terrain point in contact is appended"""
+        R = quat_to_R(quat)
+        u = np.concatenate([w, v, qd])
+        vimp = np.asarray(vimp, float)
+        cons = [c for c in self.contacts(p, R, q, u, 0.0, 0.0, 0.0, 0.0, self_collision=False)]
+        amax = np.full(6, -1.0)
+        if cons:
+            for c, vp in zip(cons, self._contact_velocities(p, R, q, u, cons)):
+                amax[c[6]] = max(amax[c[6]], max(-(c[2] @ vp), 0.0))
+                if detail is not None:
+                    detail.append((c[6], float(c[2] @ vp)))
+        return np.where(amax < 0, 0.0, np.where(vimp > 0, vimp, np.maximum(amax, 1e-6)))
+
+    def report(self, p, quat, w, v, q, qd, vimp, mu_ground, e_ground, mu_self, self_collision=True, detail=None):
+        """(rigid (13, 13), contact (13, 3)): the end-of-step report of DESIGN.md §4 at the state (p, quat, w, v_O, q,
+        qd) with the restitution episodes vimp (6).  Rigid rows: frame origin, xyzw quaternion of the FK rotation, COM
+        velocity, angular velocity.  Force rows: per contact point in contact f_n = max(k pen - [v_n < v_tgt] d (v_n -
+        v_tgt), 0), f = f_n n - mu f_n v_t / max(|v_t|, v_s); v_tgt from the body's episode (the base box: the larger of
+        its halves' targets), self-contact pairs with v_tgt = 0 and mu_self against the other body's point velocity.
+        detail (a list): one dict per contact point is appended (body, other body or None, slot, v_n, v_tgt, |v_t|,
+        the unclamped f_n, the force)."""
+        k, d, vs = self.sv["k_contact"], self.sv["d_contact"], self.sv["friction_vs"]
+        R = quat_to_R(quat)
+        u = np.concatenate([w, v, qd])
+        vimp = np.asarray(vimp, float)
+        Rs, ps, _ = self.fk(p, R, q)
+        cons = self.contacts(p, R, q, u, mu_ground, e_ground, mu_self, 0.0, self_collision)
+        pts = [(c[0], c[1]) for c in cons] + [c[4] for c in cons if c[4] is not None]
+        vc, wb, vx = self.velocities(p, R, q, u, pts)
+        rigid = np.zeros((13, 13))
+        for b in range(13):
+            rigid[b] = np.concatenate([ps[b], R_to_quat(Rs[b]), vc[b], wb[b]])
+        contact = np.zeros((13, 3))
+        vt_base = max(self._target(e_ground, vimp[4]), self._target(e_ground, vimp[5]))
+        nxt = len(cons)
+        for i, (b, local, n, pen, other, mu, slot) in enumerate(cons):
+            vp = vx[i]
+            if other is not None:
+                vp, nxt = vp - vx[nxt], nxt + 1
+            vtg = 0.0 if slot is None else (vt_base if b == 0 else self._target(e_ground, vimp[slot]))
+            vn = n @ vp
+            vt = vp - vn * n
+            raw = k * pen - (d * (vn - vtg) if vn < vtg else 0.0)
+            fn = max(raw, 0.0)
+            f = fn * n - mu * fn * vt / max(np.linalg.norm(vt), vs)
+            contact[b] += f
+            if detail is not None:
+                detail.append({"body": b, "other": None if other is None else other[0], "slot": slot, "vn": vn,
+                               "vtg": vtg, "vt": float(np.linalg.norm(vt)), "raw": raw, "force": f})
+        return rigid, contact
+
+    def switch_distance(self, p, quat, q):
+        """per body (13), the smallest distance [m] of one of its contact candidates from the surface at which it
+        switches between in and out of contact: |h - z| of a terrain point, |dist - (r_a + r_b)| of a capsule pair
+        (both bodies); inf for bodies without candidates"""
+        R = quat_to_R(quat)
+        Rs, ps, _ = self.fk(p, R, q)
+        out = np.full(13, np.inf)
+        pts = np.asarray(self.tab["contact_point"], float)
+        for b in range(13):
+            s, n = self.tab["contact_start"][b], self.tab["contact_count"][b]
+            for c in range(s, s + n):
+                x = self._points(Rs, ps, b, pts[c])
+                h = self.terrain.query(x[0], x[1])[0] if self.terrain is not None else 0.0
+                out[b] = min(out[b], abs(h - x[2]))
+        caps = _capsules(self.tab)
+        for a, bb in [(4, 10), (4, 12), (6, 10), (6, 12), (4, 6), (10, 12)]:
+            (a0, a1, ra), (b0, b1, rb) = caps[a], caps[bb]
+            ca, cb = _closest_segments(self._points(Rs, ps, a, a0), self._points(Rs, ps, a, a1),
+                                       self._points(Rs, ps, bb, b0), self._points(Rs, ps, bb, b1))
+            gap = abs(np.linalg.norm(ca - cb) - ra - rb)
+            out[a], out[bb] = min(out[a], gap), min(out[bb], gap)
         return out
 
     def step(self, p, quat, w, v, q, qd, tau, dt, mu_ground, e_ground, mu_self, e_self, f_base=None,

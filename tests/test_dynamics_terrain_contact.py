@@ -17,7 +17,8 @@ the comparison cannot pass with the terrain ignored.  The host fp32 builds' wors
 yardstick for the GPU kernels' bound in tests/test_gpu_dynamics_terrain_contact.py.
 
 Not covered: points beyond the field's edge (the header clamps, extruding the edge profile but keeping an interior
-slope in the normal), the reference's steep-slope vertex correction, the contact_forces report.
+slope in the normal) and the reference's steep-slope vertex correction.  The contact_forces / rigid_state report on
+the same field is pinned by tests/test_dynamics_report.py and tests/test_gpu_dynamics_report.py.
 """
 import numpy as np
 import pytest

@@ -373,7 +373,10 @@ T1_HD void contact_point(const DynModel& M, V3<R> x, V3<R> n, R pen, const R Vb[
   R cn = ap ? dt * k + d : (rs ? d : R(0));
   R fn_est = k * pen + (ap ? -d * vn : (rs ? d * (vtg - vn) : R(0)));
   R ct = mu * fn_est * rcp(vtn > R(M.friction_vs) ? vtn : R(M.friction_vs));
-  if (amax) *amax = *amax > -vn ? *amax : (-vn > R(0) ? -vn : R(0));
+  if (amax) {  // (against max(-v_n, 0), not -v_n: the "no contact" start value -1 is above -v_n of a point leaving at > 1 m/s)
+    const R a = -vn > R(0) ? -vn : R(0);
+    *amax = *amax > a ? *amax : a;
+  }
   // force at the current velocity (explicit part) f = (k pen - cn vn + d vtg) n - ct vt, C = cn nn^T + ct (I - nn^T)
   V3<R> f = (k * pen - cn * vn + (rs ? d * vtg : R(0))) * n - ct * vt;
   V3<R> tq = cross(x, f);
