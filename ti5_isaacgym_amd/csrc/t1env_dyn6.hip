@@ -49,10 +49,15 @@ __device__ unsigned g_t1_simd6[4096][8];
 // ticks (s_memrealtime) from its start to the end of its epilogue, summed over workgroups and launches, and the count
 __device__ unsigned long long g_t1_clock6[4];
 // and the timeline of the last launch, per workgroup: {start, W0 end, last wave's end} in 100 MHz ticks; per workgroup
-// summed over launches: {W0 lifetime, W0's S1 waits, W0's S2 waits} in shader cycles
+// summed over launches, in shader cycles: {W0 lifetime, W0's S1 waits of substeps 1+, W0's S2 waits, W0's wait at the
+// first S1 (the slowest wave's prologue), then each shift role's S2 -> S1 tails (its stores and next loads) by shift index}
+constexpr int T1_WGSUM6_N = 4 + 6;
 __device__ unsigned long long g_t1_wgtime6[4096][4];  // + [3]: W0's substep loop end
-__device__ unsigned long long g_t1_wgsum6[4096][3];
+__device__ unsigned long long g_t1_wgsum6[4096][T1_WGSUM6_N];
 #define T1_CLOCK_WAIT_BEGIN() const unsigned long long t1c_w0 = __builtin_amdgcn_s_memtime();
+#define T1_CLOCK_SHIFT_END(wi)                                                     \
+  if ((threadIdx.x & 63) == 0 && blockIdx.x < 4096 && (wi) >= 0)                   \
+    atomicAdd(&g_t1_wgsum6[blockIdx.x][4 + (wi)], __builtin_amdgcn_s_memtime() - t1c_w0);
 #define T1_CLOCK_LOOP_END()                                                        \
   if (threadIdx.x == 0 && blockIdx.x < 4096) g_t1_wgtime6[blockIdx.x][3] = __builtin_amdgcn_s_memrealtime();
 #define T1_CLOCK_WAIT_END(k)                                                       \
@@ -86,6 +91,7 @@ __device__ unsigned long long g_t1_wgsum6[4096][3];
 #define T1_CLOCK_WAVE_END() ((void)0)
 #define T1_CLOCK_WAIT_BEGIN() ((void)0)
 #define T1_CLOCK_WAIT_END(k) ((void)0)
+#define T1_CLOCK_SHIFT_END(wi) ((void)0)
 #define T1_CLOCK_LOOP_END() ((void)0)
 #endif
 
@@ -231,66 +237,148 @@ __device__ __forceinline__ void shift6_range(const uint8_t* in0, uint8_t* out0, 
 // stores slice s (after S2), holds them in registers through substep s + 1's role work (the HBM stream then spans the
 // whole substep instead of the post-S2 window alone, where its burst outlasted the core chain) and forms and stores
 // the outputs after the next S2.  A lane holds U_O chunks of the actor history and one of the critic history; a slice
-// with more chunks (fewer than 10 substeps) does the rest through shift6_f32 / _f16 at commit time.
+// with more chunks (fewer than 10 substeps) does the rest through shift6_range once the next loads are issued.
 constexpr int SHP_UO = 7, SHP_UP = 1;  // 32 rows / 10 slices / (6 x 64) lanes: 6.5 actor chunks, 0.5 critic
 struct ShiftHold {
-  float4 a[SHP_UO + SHP_UP];  // the 16-B source of each held chunk
+  u32x4 a[SHP_UO + SHP_UP];  // the 16-B source of each held chunk
 };
-template <int F, int H, bool HALF, int U>
-__device__ __forceinline__ void shp_issue(const void* in, int64_t total, int64_t r0, int64_t r1, int sl, int nsl,
-                                          int t0, int stride, float4* a) {
-  constexpr uint32_t ROW = F * H, ES = HALF ? 2 : 4;
+// One history's share of the workgroup's rows as a shift wave walks it, set up once per step (shp_setup).  What the
+// substep's fast path touches is in bytes -- a chunk is 16 B of either dtype, its source one frame (fB bytes) further
+// -- so that path holds no dtype dispatch, and the slice bounds floor(chunks * s / nsl) advance by addition (no
+// division per substep).  Every field is wave-uniform.
+struct ShpHist {
+  const uint8_t* in0;  // the workgroup's first row
+  uint8_t* out0;
+  uint32_t fB;         // one frame in bytes
+  uint32_t limB;       // in0 + limB: where a 16-B source may end at the latest (lim in bytes)
+  uint32_t lim, nel;   // shp_range's, in elements (the element path); lim clipped to what a source of these rows reaches
+  uint32_t cfull;      // chunks [0, cfull) are stored whole: inside the workgroup's rows, their source inside the buffer
+  uint32_t qn, rn;     // chunks / nsl, chunks % nsl
+  uint32_t lo, rem;    // the slice in hand: its first chunk floor(chunks * s / nsl), and (chunks * s) % nsl
+};
+template <int F, int H, bool HALF>
+__device__ __forceinline__ void shp_setup(const void* in, void* out, int64_t total, int64_t r0, int64_t r1, int nsl,
+                                          ShpHist& X) {
+  constexpr uint32_t ROW = F * H, PER = HALF ? 8 : 4, ES = HALF ? 2 : 4;
   uint32_t lo, hi, lim, nel;
-  shp_range<F, H, HALF>(total, r0, r1, sl, nsl, lo, hi, lim, nel);
-  shift_loads<F, HALF, U>(reinterpret_cast<const uint8_t*>(in) + (size_t)(r0 * ROW) * ES, lo, lim, t0, stride, a);
+  shp_range<F, H, HALF>(total, r0, r1, 0, nsl, lo, hi, lim, nel);
+  // no source of the workgroup's chunks ends past nel + F + PER: with lim clipped to it every bound below decides as
+  // with lim itself, and lim in bytes fits 32 bits
+  if (lim > nel + F + PER) lim = nel + F + PER;
+  const uint32_t n = (nel + PER - 1) / PER;
+  X.in0 = reinterpret_cast<const uint8_t*>(in) + (size_t)(r0 * ROW) * ES;
+  X.out0 = reinterpret_cast<uint8_t*>(out) + (size_t)(r0 * ROW) * ES;
+  X.fB = F * ES;
+  X.limB = lim * ES;
+  X.lim = lim;
+  X.nel = nel;
+  // chunk c is stored whole if c * PER + PER <= nel and c * PER + F + PER <= lim (shift_stores' test)
+  const uint32_t c_rows = nel / PER, c_src = lim >= F + PER ? (lim - F) / PER : 0;
+  X.cfull = c_rows < c_src ? c_rows : c_src;
+  X.qn = n / (uint32_t)nsl;
+  X.rn = n % (uint32_t)nsl;
+  X.lo = 0;
+  X.rem = 0;
+}
+// to the next slice: returns the end of the slice in hand (the first chunk of the next)
+__device__ __forceinline__ uint32_t shp_advance(ShpHist& X, uint32_t nsl) {
+  uint32_t hi = X.lo + X.qn, r = X.rem + X.rn;
+  if (r >= nsl) { r -= nsl; ++hi; }
+  X.lo = hi;
+  X.rem = r;
+  return hi;
+}
+// the exact-source loads of the U chunks a lane holds of the slice that begins at chunk lo (shift_loads, in bytes)
+typedef uint32_t shift_u4 __attribute__((ext_vector_type(4), aligned(2)));
+template <int U>
+__device__ __forceinline__ void shp_loads(const ShpHist& X, uint32_t lo, int t0, int stride, u32x4* a) {
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const uint32_t sb = (lo + (uint32_t)(t0 + u * stride)) * 16u + X.fB;
+    const uint32_t sc = sb + 16u <= X.limB ? sb : X.limB - 16u;  // tail: an in-bounds dummy
+    const shift_u4 v = *reinterpret_cast<const shift_u4*>(X.in0 + sc);
+    a[u] = u32x4{v.x, v.y, v.z, v.w};
+  }
+}
+// the whole-chunk stores of the held chunks of slice [lo, hi), back to back
+template <int U>
+__device__ __forceinline__ void shp_stores(const ShpHist& X, uint32_t lo, uint32_t hi, int t0, int stride,
+                                           const u32x4* a) {
+  const uint32_t cw = hi < X.cfull ? hi : X.cfull;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const uint32_t c = lo + (uint32_t)(t0 + u * stride);
+    if (c < cw) __builtin_nontemporal_store(a[u], reinterpret_cast<u32x4*>(X.out0 + (size_t)c * 16u));
+  }
+}
+// what the fast path leaves of slice [lo, hi): the held chunks that are not stored whole (the workgroup's last chunk,
+// the buffer's end) by the element path, and the chunks past the held ones (a slice larger than the lanes hold: fewer
+// than 10 substeps) through shift6_range -- both from memory, not from the hold
+__device__ __forceinline__ bool shp_has_rest(const ShpHist& X, uint32_t lo, uint32_t hi, int U, int stride) {
+  return hi > X.cfull || lo + (uint32_t)(U * stride) < hi;
 }
 template <int F, int H, bool HALF, int U>
-__device__ __forceinline__ void shp_commit(const void* in, void* out, int64_t total, int64_t r0, int64_t r1, int sl,
-                                           int nsl, int t0, int stride, const float4* a) {
-  constexpr uint32_t ROW = F * H, ES = HALF ? 2 : 4;
-  uint32_t lo, hi, lim, nel;
-  shp_range<F, H, HALF>(total, r0, r1, sl, nsl, lo, hi, lim, nel);
-  const uint8_t* in0 = reinterpret_cast<const uint8_t*>(in) + (size_t)(r0 * ROW) * ES;
-  uint8_t* out0 = reinterpret_cast<uint8_t*>(out) + (size_t)(r0 * ROW) * ES;
-  shift_stores<F, H, HALF, U>(in0, out0, lo, hi, lim, nel, t0, stride, a);
-  // chunks past the held ones (a slice larger than the lanes hold: fewer than 10 substeps)
+__device__ __forceinline__ void shp_rest(const ShpHist& X, uint32_t lo, uint32_t hi, int t0, int stride) {
+  constexpr uint32_t PER = HALF ? 8 : 4;
+#pragma unroll 1
+  for (int u = 0; u < U; ++u) {
+    const uint32_t c = lo + (uint32_t)(t0 + u * stride);
+    if (c >= X.cfull && c < hi) shift_chunk_elems<F, H, HALF>(X.in0, X.out0, c * PER, X.nel);
+  }
   const uint32_t rest = lo + (uint32_t)(U * stride);
-  if (rest < hi) shift6_range<F, H, HALF, 1>(in0, out0, rest, hi, lim, nel, t0, stride);
+  if (rest < hi) shift6_range<F, H, HALF, 1>(X.in0, X.out0, rest, hi, X.lim, X.nel, t0, stride);
 }
-// issue slice sl's loads into H (shift wave wi); commit slice sl from H
-__device__ __forceinline__ void shp_issue_slice(const ShiftArgs& S, int64_t r0, int64_t r1, int sl, int nsl, int wi,
-                                                int lane, ShiftHold& Hd) {
-  if (r1 <= r0 || sl >= nsl) return;
-  const int t0 = wi * 64 + lane, stride = 64 * SHIFT6_WAVES;
+// a shift wave's state of the step: both histories' walks and the lane's place among the shift waves' lanes
+struct ShiftWalk {
+  ShpHist o, p;  // the actor history, the critic history
+  int t0;        // the lane's index among the 6 x 64 shift lanes
+  bool on;       // the workgroup has rows (and the wave shifts)
+};
+// before the loop: the walks set up (the one place that looks at the dtype) and slice 0's loads issued
+__device__ __forceinline__ void shp_begin(const ShiftArgs& S, int64_t r0, int64_t r1, int nsl, int wi, int lane,
+                                          ShiftWalk& W, ShiftHold& Hd) {
+  W.on = wi >= 0 && r1 > r0 && nsl > 0;
+  W.t0 = wi * 64 + lane;
+  if (!W.on) return;
   if (S.half) {
-    shp_issue<T1_NOBS, T1_HIST, true, SHP_UO>(S.obs_in, S.total_obs, r0, r1, sl, nsl, t0, stride, Hd.a);
-    shp_issue<T1_NPRIV, T1_CHIST, true, SHP_UP>(S.priv_in, S.total_priv, r0, r1, sl, nsl, t0, stride, Hd.a + SHP_UO);
+    shp_setup<T1_NOBS, T1_HIST, true>(S.obs_in, S.obs_out, S.total_obs, r0, r1, nsl, W.o);
+    shp_setup<T1_NPRIV, T1_CHIST, true>(S.priv_in, S.priv_out, S.total_priv, r0, r1, nsl, W.p);
   } else {
-    shp_issue<T1_NOBS, T1_HIST, false, SHP_UO>(S.obs_in, S.total_obs, r0, r1, sl, nsl, t0, stride, Hd.a);
-    shp_issue<T1_NPRIV, T1_CHIST, false, SHP_UP>(S.priv_in, S.total_priv, r0, r1, sl, nsl, t0, stride, Hd.a + SHP_UO);
+    shp_setup<T1_NOBS, T1_HIST, false>(S.obs_in, S.obs_out, S.total_obs, r0, r1, nsl, W.o);
+    shp_setup<T1_NPRIV, T1_CHIST, false>(S.priv_in, S.priv_out, S.total_priv, r0, r1, nsl, W.p);
   }
+  constexpr int stride = 64 * SHIFT6_WAVES;
+  shp_loads<SHP_UO>(W.o, 0, W.t0, stride, Hd.a);
+  shp_loads<SHP_UP>(W.p, 0, W.t0, stride, Hd.a + SHP_UO);
 }
-__device__ __forceinline__ void shp_commit_slice(const ShiftArgs& S, int64_t r0, int64_t r1, int sl, int nsl, int wi,
-                                                 int lane, const ShiftHold& Hd) {
-  if (r1 <= r0 || sl >= nsl) return;
-  const int t0 = wi * 64 + lane, stride = 64 * SHIFT6_WAVES;
-  if (S.half) {
-    shp_commit<T1_NOBS, T1_HIST, true, SHP_UO>(S.obs_in, S.obs_out, S.total_obs, r0, r1, sl, nsl, t0, stride, Hd.a);
-    shp_commit<T1_NPRIV, T1_CHIST, true, SHP_UP>(S.priv_in, S.priv_out, S.total_priv, r0, r1, sl, nsl, t0, stride,
-                                                 Hd.a + SHP_UO);
-  } else {
-    shp_commit<T1_NOBS, T1_HIST, false, SHP_UO>(S.obs_in, S.obs_out, S.total_obs, r0, r1, sl, nsl, t0, stride, Hd.a);
-    shp_commit<T1_NPRIV, T1_CHIST, false, SHP_UP>(S.priv_in, S.priv_out, S.total_priv, r0, r1, sl, nsl, t0, stride,
-                                                  Hd.a + SHP_UO);
+// a shift role's tail of substep `sub`, after S2: one wait for the held sources (loaded a substep ago; nothing else of
+// the wave's is outstanding), slice `sub`'s whole-chunk stores back to back, slice `sub + 1`'s loads right behind them
+// -- no wait for the stores: gfx950 counts loads and stores in one vmcnt, so a wait here would hold the wave until
+// its streaming stores are acknowledged, and the core wave at the next S1 with it -- and only then the rare rest
+__device__ __forceinline__ void shp_step(const ShiftArgs& S, int sub, int nsub, ShiftWalk& W, ShiftHold& Hd) {
+  if (!W.on) return;
+  constexpr int stride = 64 * SHIFT6_WAVES;
+  const uint32_t lo_o = W.o.lo, lo_p = W.p.lo;
+  const uint32_t hi_o = shp_advance(W.o, (uint32_t)nsub), hi_p = shp_advance(W.p, (uint32_t)nsub);
+  static_assert(SHP_UO + SHP_UP == 8, "the hold passes through one asm statement");
+  // every held source through one empty asm: the wave waits once, before the first store, not once per store
+  asm volatile("" : "+v"(Hd.a[0]), "+v"(Hd.a[1]), "+v"(Hd.a[2]), "+v"(Hd.a[3]), "+v"(Hd.a[4]), "+v"(Hd.a[5]),
+                    "+v"(Hd.a[6]), "+v"(Hd.a[7]));
+  shp_stores<SHP_UO>(W.o, lo_o, hi_o, W.t0, stride, Hd.a);
+  shp_stores<SHP_UP>(W.p, lo_p, hi_p, W.t0, stride, Hd.a + SHP_UO);
+  if (sub + 1 < nsub) {
+    shp_loads<SHP_UO>(W.o, hi_o, W.t0, stride, Hd.a);
+    shp_loads<SHP_UP>(W.p, hi_p, W.t0, stride, Hd.a + SHP_UO);
   }
-}
-// a shift role's tail of substep `sub`, after S2: commit slice `sub` (its loads issued a substep ago), then issue
-// slice `sub + 1`'s loads (wi: shift6_index of the role)
-__device__ __forceinline__ void shp_step(const ShiftArgs& S, int64_t r0, int64_t r1, int sub, int nsub, int wi,
-                                         int lane, ShiftHold& Hd) {
-  if (wi < 0) return;
-  shp_commit_slice(S, r0, r1, sub, nsub, wi, lane, Hd);
-  shp_issue_slice(S, r0, r1, sub + 1, nsub, wi, lane, Hd);
+  if (__builtin_expect(shp_has_rest(W.o, lo_o, hi_o, SHP_UO, stride) || shp_has_rest(W.p, lo_p, hi_p, SHP_UP, stride), 0)) {
+    if (S.half) {
+      shp_rest<T1_NOBS, T1_HIST, true, SHP_UO>(W.o, lo_o, hi_o, W.t0, stride);
+      shp_rest<T1_NPRIV, T1_CHIST, true, SHP_UP>(W.p, lo_p, hi_p, W.t0, stride);
+    } else {
+      shp_rest<T1_NOBS, T1_HIST, false, SHP_UO>(W.o, lo_o, hi_o, W.t0, stride);
+      shp_rest<T1_NPRIV, T1_CHIST, false, SHP_UP>(W.p, lo_p, hi_p, W.t0, stride);
+    }
+  }
 }
 
 __device__ __forceinline__ int shift6_index(int role) {  // the role's index among the shifting roles, -1: none
@@ -493,6 +581,7 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
 
   if (role == 4) {
     // ======== W4: base -- the actions, PD torques, the base block and both base-box halves (their restitution episode)
+    T1_PROF_MARK(20);  // role entry (tools/isa_phases.py: the prologue's memory round trips, to mark 0)
     const BaseParams<float>& PB = lds.pb[lane];  // W0 stores it before the first S1 (LDS, not registers held across
                                                  // the loop); read from the first substep on
     // the friction and restitution, lag, force and episode loads, then the actions and PD constants below, before the
@@ -503,28 +592,53 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
     const RngKey K = rng_key(C.seed, (uint32_t)(C.env_offset + n), ctr);
     const V3<float> ef = v3<float>(B.applied_force[n * 3 + 0], B.applied_force[n * 3 + 1], B.applied_force[n * 3 + 2]);
     float vi_b = B.contact_vimp[(size_t)n * NVIMP + vimp_base(leg)];
-    {  // actions = clip(actions) into the step's history slot, the PD constants and action ring staged
+    {  // actions = clip(actions) into the step's history slot, the PD constants and action ring staged.  Every load of
+       // the prologue is issued before its first LDS write -- the whole action ring too, the slot this step overwrites
+       // included (in bounds), chosen against by a select: a load behind `s == cs` is a branch around it and a
+       // memory round trip per element -- so the prologue costs one memory latency, not one per value
       PdStage<64>& P = lds.pd;
-      float a[NLEG];
+      float a[NLEG], kp[NLEG], kd[NLEG], off[NLEG], visc[NLEG], coul[NLEG], ring[4][NLEG];
 #pragma unroll
-      for (int k = 0; k < NLEG; ++k) a[k] = fminf(fmaxf(actions[n * 12 + j0 + k], -C.clip_actions), C.clip_actions);
-      const int cs = (int)(ctr & 3u);
+      for (int k = 0; k < NLEG; ++k) a[k] = actions[n * 12 + j0 + k];
 #pragma unroll
       for (int k = 0; k < NLEG; ++k) {
         const int j = j0 + k;
-        P.kp[k][lane] = B.kp[n * 12 + j];
-        P.kd[k][lane] = B.kd[n * 12 + j];
-        P.off[k][lane] = B.motor_offsets[n * 12 + j];
-        P.visc[k][lane] = B.viscous[n * 12 + j];
-        P.coul[k][lane] = B.coulomb[n * 12 + j];
+        kp[k] = B.kp[n * 12 + j];
+        kd[k] = B.kd[n * 12 + j];
+        off[k] = B.motor_offsets[n * 12 + j];
+        visc[k] = B.viscous[n * 12 + j];
+        coul[k] = B.coulomb[n * 12 + j];
       }
 #pragma unroll
       for (int s = 0; s < 4; ++s)
 #pragma unroll
-        for (int k = 0; k < NLEG; ++k)
-          P.act[s][k][lane] = s == cs ? a[k] * C.action_scale : B.act_hist[((size_t)n * 4 + s) * 12 + j0 + k];
+        for (int k = 0; k < NLEG; ++k) ring[s][k] = B.act_hist[((size_t)n * 4 + s) * 12 + j0 + k];
+      EpiStage<NE6, 256> ES;  // the epilogue's inputs (below): their loads in the same batch
+      if (FUSED) epi_stage_load<NE6, 256>(B, N, (int)r0, (int)threadIdx.x - 256, ES);
+#pragma unroll
+      for (int s = 0; s < 4; ++s)  // through an empty asm: a load whose only use is a select is sunk behind its condition
+        asm volatile("" : "+v"(ring[s][0]), "+v"(ring[s][1]), "+v"(ring[s][2]), "+v"(ring[s][3]), "+v"(ring[s][4]),
+                          "+v"(ring[s][5]));
+#pragma unroll
+      for (int k = 0; k < NLEG; ++k) a[k] = fminf(fmaxf(a[k], -C.clip_actions), C.clip_actions);
+      const int cs = (int)(ctr & 3u);
+#pragma unroll
+      for (int k = 0; k < NLEG; ++k) {
+        P.kp[k][lane] = kp[k];
+        P.kd[k][lane] = kd[k];
+        P.off[k][lane] = off[k];
+        P.visc[k][lane] = visc[k];
+        P.coul[k][lane] = coul[k];
+      }
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int k = 0; k < NLEG; ++k) P.act[s][k][lane] = s == cs ? a[k] * C.action_scale : ring[s][k];
 #pragma unroll
       for (int k = 0; k < NLEG; ++k) lds.act[j0 + k][e] = a[k];
+      // the epilogue's inputs the step does not change, staged by W4-W7 before their first substep (staged by W4 alone
+      // in the first substep's idle S2 -> S1 window instead: 0.1301 vs 0.1269 ms, its loop's registers spill, r05stage)
+      if (FUSED) epi_stage_store<NE6, 256>(N, (int)r0, (int)threadIdx.x - 256, ES, lds.epi);
       if (active) {
         float* slot = B.act_hist + ((size_t)n * 4 + cs) * 12;
 #pragma unroll
@@ -534,9 +648,6 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
         }
       }
     }
-    // the epilogue's inputs the step does not change, staged by W4-W7 before their first substep (staged by W4 alone
-    // in the first substep's idle S2 -> S1 window instead: 0.1301 vs 0.1269 ms, its loop's registers spill, r05stage)
-    if (FUSED) stage_epilogue_inputs<NE6, 256>(B, N, (int)r0, (int)threadIdx.x - 256, lds.epi);
     int cb, ce;
     base_contact_range(M, leg, cb, ce);
     T1_PROF_MARK(0);
@@ -639,12 +750,14 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
 
   if (role != 0) {
     // ======== the term roles W1-W3, W5-W7
+    T1_PROF_MARK(21);  // role entry; the staging ends at mark 22
     const int wi = shift6_index(role);
     const float mu = 0.5f * (B.friction[n] + M.ground_friction);  // robot shape vs ground (PhysX average)
     const float mu_self = B.friction[n];                          // robot shape vs robot shape
     const float eg = ground_restitution(M, B.restitution[n]);
     // the epilogue's inputs the step does not change, staged by W4-W7 before their first substep
     if (FUSED && wave >= 4) stage_epilogue_inputs<NE6, 256>(B, N, (int)r0, (int)threadIdx.x - 256, lds.epi);
+    T1_PROF_MARK(22);
     const int bsh = 1 + 6 * leg + K_SHANK, bft = 1 + 6 * leg + K_FOOT;
     const int half = role >= 4 ? 1 : 0;  // roles 2 / 3: points 0-3, 6 / 7: points 4-7
     // each role its own substep loop (the register allocation of one role's loop does not carry the others' values)
@@ -653,7 +766,8 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
       LegParams<float> PL;
       load_leg_params(M, B, n, j0, PL);
       ShiftHold hold;  // the pipelined history shift's loads in flight (its own live range per role loop)
-      if (wi >= 0) shp_issue_slice(S, r0, r1, 0, nsub, wi, lane, hold);
+      ShiftWalk walk;
+      shp_begin(S, r0, r1, nsub, wi, lane, walk, hold);
       for (int sub = 0; sub < nsub; ++sub) {
         T1_PROF_MARK(4);
         __syncthreads();  // S1
@@ -674,12 +788,15 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
         T1_PROF_MARK(2);
         __syncthreads();  // S2
         T1_PROF_MARK(3);
-        shp_step(S, r0, r1, sub, nsub, wi, lane, hold);
+        T1_CLOCK_WAIT_BEGIN();
+        shp_step(S, sub, nsub, walk, hold);
+        T1_CLOCK_SHIFT_END(wi);
       }
     } else if (role == 5) {
       // ---- W5: self-contact terms of the shank and foot
       ShiftHold hold;  // the pipelined history shift's loads in flight (its own live range per role loop)
-      if (wi >= 0) shp_issue_slice(S, r0, r1, 0, nsub, wi, lane, hold);
+      ShiftWalk walk;
+      shp_begin(S, r0, r1, nsub, wi, lane, walk, hold);
       for (int sub = 0; sub < nsub; ++sub) {
         T1_PROF_MARK(4);
         __syncthreads();  // S1
@@ -713,7 +830,9 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
         T1_PROF_MARK(2);
         __syncthreads();  // S2
         T1_PROF_MARK(3);
-        shp_step(S, r0, r1, sub, nsub, wi, lane, hold);
+        T1_CLOCK_WAIT_BEGIN();
+        shp_step(S, sub, nsub, walk, hold);
+        T1_CLOCK_SHIFT_END(wi);
       }
     } else {
       // ---- W2 / W6: shank terrain, W3 / W7: foot terrain (one half of the body's points each); W6 also records the
@@ -726,7 +845,8 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
       const int b = shank ? bsh : bft;
       const int c0 = M.contact_start[b] + half * (T1_POINTS_PER_BODY / 2);
       ShiftHold hold;  // the pipelined history shift's loads in flight (its own live range per role loop)
-      if (wi >= 0) shp_issue_slice(S, r0, r1, 0, nsub, wi, lane, hold);
+      ShiftWalk walk;
+      shp_begin(S, r0, r1, nsub, wi, lane, walk, hold);
       for (int sub = 0; sub < nsub; ++sub) {
         T1_PROF_MARK(4);
         __syncthreads();  // S1
@@ -758,7 +878,9 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
         T1_PROF_MARK(2);
         __syncthreads();  // S2
         T1_PROF_MARK(3);
-        shp_step(S, r0, r1, sub, nsub, wi, lane, hold);
+        T1_CLOCK_WAIT_BEGIN();
+        shp_step(S, sub, nsub, walk, hold);
+        T1_CLOCK_SHIFT_END(wi);
       }
     }
     T1_PROF_MARK(4);
@@ -887,7 +1009,7 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
     {
       T1_CLOCK_WAIT_BEGIN();
       __syncthreads();  // S1: the substep state published
-      T1_CLOCK_WAIT_END(1);
+      T1_CLOCK_WAIT_END(sub == 0 ? 3 : 1);
     }
     T1_PROF_MARK(1);
     const DynModel& M = model_in_loop(lds.model);
@@ -1030,9 +1152,9 @@ extern "C" int t1env_debug_wgtime6(unsigned long long* out, int blocks) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_t1_wgtime6), sizeof(unsigned long long) * 4 * (size_t)blocks);
 }
 extern "C" int t1env_debug_wgsum6(unsigned long long* out, int blocks, int reset) {
-  hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_t1_wgsum6), sizeof(unsigned long long) * 3 * (size_t)blocks);
+  hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_t1_wgsum6), sizeof(unsigned long long) * T1_WGSUM6_N * (size_t)blocks);
   if (e == hipSuccess && reset) {
-    static unsigned long long zero[4096][3] = {};
+    static unsigned long long zero[4096][T1_WGSUM6_N] = {};
     e = hipMemcpyToSymbol(HIP_SYMBOL(g_t1_wgsum6), zero, sizeof(zero));
   }
   return (int)e;

@@ -197,21 +197,28 @@ template <typename T> __device__ __forceinline__ float stage_bits(T v) {
   if constexpr (sizeof(T) == 4) return __builtin_bit_cast(float, v);
   else return __int_as_float((int)v);
 }
+// A thread past the end of a run (the last round of a run that is no multiple of NT, or a workgroup with nv < NE envs)
+// takes the run's last word instead: it loads that word and writes it to that word's place, the same value another
+// thread writes there.  So neither the loads nor the LDS writes stand behind a bound -- hipcc makes a branch of each
+// such bound, with a wait (and at -O1 a scratch reload, which drains every load before it) where the branches join:
+// a memory round trip per element instead of one for the staging.
 template <int NE, int NT, int L, typename T>
 __device__ __forceinline__ void stage_ld(const T* __restrict__ src, int nb, int nv, int t, float (&v)[stage_n<NE, NT, L>()]) {
   const T* base = src + (size_t)nb * L;
+  const int last = nv * L - 1;  // nv >= 1: every workgroup has an env
 #pragma unroll
   for (int i = 0; i < stage_n<NE, NT, L>(); ++i) {
     const int e = t + NT * i;
-    v[i] = e < nv * L ? stage_bits(base[e]) : 0.0f;
+    v[i] = stage_bits(base[e < last ? e : last]);
   }
 }
 template <int NE, int NT, int L>
 __device__ __forceinline__ void stage_st(float (*dst)[NE], int nv, int t, const float (&v)[stage_n<NE, NT, L>()]) {
+  const int last = nv * L - 1;
 #pragma unroll
   for (int i = 0; i < stage_n<NE, NT, L>(); ++i) {
-    const int e = t + NT * i;
-    if (e < nv * L) dst[e % L][e / L] = v[i];
+    const int e = t + NT * i, ec = e < last ? e : last;
+    dst[ec % L][ec / L] = v[i];
   }
 }
 // the staged values of one thread between its loads and its LDS writes (epi_stage_load / epi_stage_store)
@@ -249,8 +256,8 @@ __device__ __forceinline__ void epi_stage_load(const t1env_buffers& B, int N, in
   stage_ld<NE, NT, 1>(B.imu_lag_timestep, nb, nv, t, V.il);
 #pragma unroll
   for (int i = 0; i < EpiStage<NE, NT>::NES; ++i) {  // episode_sums is [reward][env]: already row-contiguous
-    const int e = t + NT * i;
-    V.es[i] = e < T1_NREW * nv ? B.episode_sums[(size_t)(e / nv) * N + nb + e % nv] : 0.0f;
+    const int e = t + NT * i, ec = e < T1_NREW * nv ? e : T1_NREW * nv - 1;  // past the end: the last word, as stage_ld
+    V.es[i] = B.episode_sums[(size_t)(ec / nv) * N + nb + ec % nv];
   }
 }
 template <int NE, int NT>
@@ -278,8 +285,8 @@ __device__ __forceinline__ void epi_stage_store(int N, int nb, int t, const EpiS
   stage_st<NE, NT, 1>(E + E_IL, nv, t, V.il);
 #pragma unroll
   for (int i = 0; i < EpiStage<NE, NT>::NES; ++i) {
-    const int e = t + NT * i;
-    if (e < T1_NREW * nv) E[E_ESUM + e / nv][e % nv] = V.es[i];
+    const int e = t + NT * i, ec = e < T1_NREW * nv ? e : T1_NREW * nv - 1;
+    E[E_ESUM + ec / nv][ec % nv] = V.es[i];
   }
 }
 template <int NE, int NT>

@@ -4,6 +4,11 @@ adds the deltas to two device counters), against the step time -- to tell a cloc
 mode when a build's step time differs across processes (VERDICT r5 #1b, the -O2 slow mode).
 
     T1ENV_LIB=ti5_isaacgym_amd/_lib/var/<probe build>.so python tools/clock_probe.py [--steps 300]
+
+The per-workgroup sums split W0's S1 waits into the first S1 of the launch (W0 waits there for the slowest wave's
+prologue: the staging loads) and the S1s of substeps 1+ (it waits for the shift waves' S2 -> S1 tails: their stores and
+next loads), and give each shift role's S2 -> S1 tail by shift index (roles 1, 2, 3, 5, 6, 7).  The modes of a build
+are per process: run it in several fresh processes.
 """
 import argparse
 import ctypes
@@ -17,6 +22,9 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ti5_isaacgym_amd import make_t1_env  # noqa: E402
+
+
+NSUM = 10  # T1_WGSUM6_N: W0 life, S1 waits of substeps 1+, S2 waits, first S1 wait, six shift roles' S2 -> S1 tails
 
 
 def main():
@@ -36,7 +44,7 @@ def main():
     out = np.zeros(4, np.uint64)
     lib.t1env_debug_clock6(out.ctypes.data_as(ctypes.c_void_p), 1)   # read and reset
     wg = (N + 31) // 32
-    sums = np.zeros((wg, 3), np.uint64)
+    sums = np.zeros((wg, NSUM), np.uint64)
     lib.t1env_debug_wgsum6(sums.ctypes.data_as(ctypes.c_void_p), wg, 1)
     t0 = time.perf_counter()
     for i in range(a.steps):
@@ -52,6 +60,7 @@ def main():
     per = sums.astype(np.float64) / a.steps / (mhz if mhz else 2400.0)   # us per launch
     ttype = (np.arange(wg) * 32) // max(1, N // 20)
     by_type = {int(k): [round(float(per[ttype == k, j].mean()), 2) for j in range(3)] for k in np.unique(ttype)}
+    mean = [round(float(x), 2) for x in per.mean(0)]
     slow = np.argsort(-per[:, 0])[:8]
     if a.dump:
         np.save(a.dump, per)
@@ -77,7 +86,11 @@ def main():
                                          "slowest_end_wgs": [[int(b), round(float(loop_t[b]), 2), round(float(epi_t[b]), 2),
                                                               int(rs[b])] for b in np.argsort(-end)[:6]]},
                       "per_wg_us_life_s1wait_s2wait_q": [q(per[:, j]) for j in range(3)],
-                      "by_terrain_type_life_s1_s2": by_type,
+                      "w0_us_mean": {"life": mean[0], "first_s1_wait": mean[3], "s1_waits_substeps_1plus": mean[1],
+                                     "s2_waits": mean[2]},
+                      "first_s1_wait_q": q(per[:, 3]),
+                      "shift_role_s2_to_s1_us_per_launch_mean": dict(zip(("W1", "W2", "W3", "W5", "W6", "W7"), mean[4:])),
+                      "by_terrain_type_life_s1sub1plus_s2": by_type,
                       "slowest_wgs": [[int(b), [round(float(x), 2) for x in per[b]]] for b in slow],
                       "lib": os.path.basename(os.environ["T1ENV_LIB"])}))
 
