@@ -37,6 +37,15 @@ int t1policy_conv1d_pack_weights(const float* weight, void* frag, int channels, 
 int t1policy_conv1d_forward_packed(const float* x, const void* frag, const float* bias, float* y, int batch,
                                    int channels, int length, int out_channels, int kernel, int stride, void* stream);
 
+/* t1policy_conv1d_forward_packed on an fp16 x (batch, channels, length) -- the env's fp16 observation histories
+ * (t1env_config.obs_half), read in place without a widened copy: same fragments, bias, y and return codes.  An fp16
+ * input is its own hi part with a zero lo part, so the result equals t1policy_conv1d_forward_packed on the widened x up
+ * to fp32 summation order (the lo.hi products it drops are exact zeros; within 1e-5 * (1 + |y|) of an fp64 conv of the
+ * widened x, tests/test_gpu_policy_fp16_obs.py).  x 4-byte aligned (a 2-byte-aligned base returns -1);
+ * batch * channels * length * 2 < 2^31.  T1POLICY_CONV=regs has no fp16 instance (the default kernel runs). */
+int t1policy_conv1d_forward_packed_h(const void* x, const void* frag, const float* bias, float* y, int batch,
+                                     int channels, int length, int out_channels, int kernel, int stride, void* stream);
+
 /* The rest of the rollout's act() after the first conv, one fused kernel (t1policy_heads.hip): the history tail
  * (conv2 + ReLU, flatten, 96 -> 128 ELU -> 64), the state estimator (235 -> 256 -> 128 -> 64 -> 3, ELU), the actor
  * ([short | estimate | code] 302 -> 512 -> 256 -> 128 -> 12, ELU), the critic (219 -> 768 -> 256 -> 128 -> 1, ELU),
@@ -61,6 +70,15 @@ int t1policy_heads_forward(const uint64_t* params, const int* dims, const void* 
                            const float* obs, int obs_cols, const float* critic_obs, int critic_cols, const float* eps,
                            float* mean, float* actions, float* sigma, float* logp, float* value, int batch,
                            void* stream);
+/* t1policy_heads_forward on fp16 obs (batch, obs_cols) and fp16 critic_obs (batch, 219), any 2-byte alignment (an odd
+ * address returns -1); y1, eps and every output fp32 as there; same params / dims / frag and return codes (1 also under
+ * T1POLICY_HEADS64=0, which has no fp16 instance).  The kernel stages each fp16 value as its own hi part with a zero lo
+ * part -- the split of the widened value -- so every output equals t1policy_heads_forward on the widened (finite)
+ * inputs bit for bit (tests/test_gpu_policy_fp16_obs.py). */
+int t1policy_heads_forward_h(const uint64_t* params, const int* dims, const void* frag, const float* y1,
+                             const void* obs, int obs_cols, const void* critic_obs, int critic_cols,
+                             const float* eps, float* mean, float* actions, float* sigma, float* logp,
+                             float* value, int batch, void* stream);
 
 /* The same first conv in the PPO update under the opt-in bf16 update (t1policy_train.hip), forward and weight
  * gradient on bf16 inputs without the unfolded copy (the autograd path dh_policy.conv1d_as_gemm unfolds 545 MB per

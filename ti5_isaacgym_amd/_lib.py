@@ -103,7 +103,7 @@ POLICY_EXPORTS = ["t1policy_conv1d_forward", "t1policy_history_rows", "t1policy_
                   "t1policy_slice_sum", "t1policy_linear_wgrad_workspace_bytes", "t1policy_linear_wgrad_bf16",
                   "t1policy_fold_rows", "t1policy_gather_rows", "t1policy_conv1_wgrad_f32",
                   "t1policy_linear_wgrad_f32", "t1policy_gemm_nt_f32", "t1policy_gemm_f32",
-                  "t1policy_linear_wgrad_f32x"]
+                  "t1policy_linear_wgrad_f32x", "t1policy_conv1d_forward_packed_h", "t1policy_heads_forward_h"]
 
 _lib = None
 
@@ -143,6 +143,8 @@ def load():
         "t1policy_conv1d_frag_bytes": ([], C.c_int),
         "t1policy_conv1d_pack_weights": ([vp, vp, i32, i32, i32, vp], C.c_int),
         "t1policy_conv1d_forward_packed": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], C.c_int),
+        "t1policy_conv1d_forward_packed_h": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], C.c_int),
+        "t1policy_heads_forward_h": ([vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp], C.c_int),
         "t1policy_heads_frag_bytes": ([], C.c_int),
         "t1policy_heads_pack": ([vp, vp, vp, vp], C.c_int),
         "t1policy_heads_forward": ([vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp], C.c_int),

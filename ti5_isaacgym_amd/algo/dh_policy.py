@@ -494,7 +494,9 @@ def _mlp(sizes, act):
 def conv1d_direct(x, conv):
     """Inference forward of a (B, C, L) Conv1d as the HIP direct-conv kernel (include/t1policy.h), channels-last
     (B, Lout, O) like conv1d_as_gemm: one pass over x instead of the unfolded-row copy plus a GEMM.  Returns None for
-    a shape the library has no instance of (the caller keeps the GEMM path)."""
+    a shape the library has no instance of (the caller keeps the GEMM path).  An fp16 x (the env's fp16 histories) is
+    read as it is by the packed kernel's fp16 instance (t1policy_conv1d_forward_packed_h, y fp32 all the same); None
+    too for an fp16 x the kernel cannot take (a base off a 4-byte boundary, 2 GiB or more)."""
     from .. import _lib
     lib = _lib.load()
     k, st = conv.kernel_size[0], conv.stride[0]
@@ -502,10 +504,16 @@ def conv1d_direct(x, conv):
     B, C, L = x.shape
     O = conv.out_channels
     lout = (L - k) // st + 1
+    if x.dtype == torch.float16 and (x.data_ptr() % 4 != 0 or B * C * L * 2 >= 2 ** 31):
+        return None
     bias = conv.bias.detach().contiguous()
     y = torch.empty(B, lout, O, device=x.device, dtype=torch.float32)
     stream = torch.cuda.current_stream(x.device).cuda_stream
-    if x.data_ptr() % 16 == 0 and B * C * L * 4 < 2 ** 31:
+    if x.dtype == torch.float16:
+        frag = packed_conv_weights(conv, stream)
+        rc = 1 if frag is None else lib.t1policy_conv1d_forward_packed_h(
+            x.data_ptr(), frag.data_ptr(), bias.data_ptr(), y.data_ptr(), B, C, L, O, k, st, stream)
+    elif x.data_ptr() % 16 == 0 and B * C * L * 4 < 2 ** 31:
         frag = packed_conv_weights(conv, stream)
         rc = 1 if frag is None else lib.t1policy_conv1d_forward_packed(
             x.data_ptr(), frag.data_ptr(), bias.data_ptr(), y.data_ptr(), B, C, L, O, k, st, stream)
@@ -757,13 +765,15 @@ def _heads_layers(ac):
 def heads_forward(ac, obs, critic_obs, eps):
     """The rollout's act() after the first conv as the fused HIP kernel (t1policy_heads_forward): returns mean,
     actions = mean + std eps, sigma (B, 12), log-prob (B,) and value (B, 1) -- DHPPO._act_body's outputs -- or None
-    when the model or inputs have no compiled instance (the caller keeps the torch path).  The weights are packed
+    when the model or inputs have no compiled instance (the caller keeps the torch path).  obs and critic_obs are
+    both fp32 or both fp16 (the env's fp16 histories, read in place: the fp16 conv, then t1policy_heads_forward_h, the
+    results of the fp32 kernels on the widened inputs); mixed dtypes return None.  The weights are packed
     into the kernel's split fp16 fragments when a parameter changed (packed_heads_weights); a captured act() graph
     reads them in place and is refreshed before each replay."""
     from .. import _lib
     layers = _heads_layers(ac)
-    if (layers is None or not obs.is_cuda or obs.dtype != torch.float32 or critic_obs.dtype != torch.float32
-            or obs.dim() != 2 or critic_obs.dim() != 2 or eps.shape != (obs.shape[0], ac.std.numel())):
+    if (layers is None or not obs.is_cuda or obs.dtype not in (torch.float32, torch.float16)
+            or critic_obs.dtype != obs.dtype or obs.dim() != 2 or critic_obs.dim() != 2 or eps.shape != (obs.shape[0], ac.std.numel())):
         return None
     # the kernel reads critic_obs and obs row by row up to the batch: shapes it was not built for are refused here,
     # not read out of bounds on the device (ADVICE r4)
@@ -790,9 +800,10 @@ def heads_forward(ac, obs, critic_obs, eps):
     actions, sigma = torch.empty_like(mean), torch.empty_like(mean)
     logp = torch.empty(B, device=dev)
     value = torch.empty(B, 1, device=dev)
-    rc = lib.t1policy_heads_forward(ptrs_c, dims_c, frag.data_ptr(), y1.data_ptr(), obs.data_ptr(), obs.shape[1],
-                                    critic_obs.data_ptr(), critic_obs.shape[1], eps.data_ptr(), mean.data_ptr(),
-                                    actions.data_ptr(), sigma.data_ptr(), logp.data_ptr(), value.data_ptr(), B, stream)
+    entry = lib.t1policy_heads_forward_h if obs.dtype == torch.float16 else lib.t1policy_heads_forward
+    rc = entry(ptrs_c, dims_c, frag.data_ptr(), y1.data_ptr(), obs.data_ptr(), obs.shape[1], critic_obs.data_ptr(),
+               critic_obs.shape[1], eps.data_ptr(), mean.data_ptr(), actions.data_ptr(), sigma.data_ptr(),
+               logp.data_ptr(), value.data_ptr(), B, stream)
     if rc == 1:
         return None
     if rc != 0:

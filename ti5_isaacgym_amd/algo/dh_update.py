@@ -189,7 +189,17 @@ class DHPPO:
         eps: the N(0, 1) draw of the mean's shape, made by the caller (the graphed act() draws it before each replay,
         so its graph holds no RNG kernel); None: drawn here."""
         ac = self.actor_critic
-        obs, critic_obs = obs.float(), critic_obs.float()   # fp16 env histories (state_dtype="fp16"): no-op for fp32
+        if (FUSED_ACT and obs.is_cuda and critic_obs.is_cuda
+                and obs.dtype == torch.float16 and critic_obs.dtype == torch.float16):
+            # fp16 env histories (state_dtype="fp16"): the fused kernels read them in place, no fp32 copy (0.4 GB
+            # written and read again per act() at 32768 envs).  A refused call retries below on the cast, with its draw
+            if eps is None:
+                eps = torch.randn(obs.shape[0], ac.std.numel(), device=obs.device)
+            out = heads_forward(ac, obs, critic_obs, eps)
+            if out is not None:
+                mean, actions, sigma, logp, value = out
+                return actions, value, logp, mean, sigma
+        obs, critic_obs = obs.float(), critic_obs.float()   # fp16 histories on the fall-through: no-op for fp32
         if obs.is_cuda and FUSED_ACT:
             # the fused HIP heads (t1policy_heads_forward): the same draw (randn of the mean's shape), one kernel for
             # every layer after the first conv plus the sample and its log-prob

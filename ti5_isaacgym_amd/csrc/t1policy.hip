@@ -355,6 +355,95 @@ void k_conv1d_pair(const float* __restrict__ x, const h8* __restrict__ frag, con
   }
 }
 
+// k_conv1d_pair_h: k_conv1d_pair on an fp16 x (the env's fp16 histories, cfg.env.state_dtype = "fp16"), the same
+// fragments, grid rule and output.  An fp16 input is its own hi part and its lo part is exactly 0, so the staging is a
+// straight copy of the sample's 1551 dwords (no split, no lo plane: half the LDS of the fp32 kernel) and the lo.hi MFMA
+// is dropped: two MFMAs per K-step, ah.bh -> acc0, ah.bl -> acc1, the same epilogue.  A sample is 6204 B, so from a
+// 4-byte-aligned x every sample is dword-aligned (and no more: 8-byte loads would fit every other sample only); each
+// wave loads 776 / 775 dwords of it, 13 per lane.
+// A lane's A fragment is the 6 halves from half (4 s + kg) 47 + 3 rr = 188 s + (47 kg + 3 rr) of the staged sample: its
+// parity, (kg + rr) & 1, is the lane's own in every K-step.  Each step reads the 4 dwords from the one holding the
+// first half (dword-aligned: two ds_read2_b32; a wider DS read off its natural alignment is replayed) and a lane of odd
+// parity shifts the 8 halves down by one: three v_alignbit_b32 by the lane's 0 or 16.  No 16-bit LDS reads.
+constexpr int CH_WORDS = CV_C * CV_L / 2;                          // 1551 dwords of a sample
+constexpr int CH_LDS = CV_CPAD * CV_L / 2;                         // 1598 staged (the 2 zero channels: 47 more)
+constexpr int CH_HALF = (CH_WORDS + 1) / 2;                        // 776 dwords of a sample per wave
+constexpr int CH_PER_LANE = (CH_HALF + 63) / 64;                   // 13
+static_assert(CV_C * CV_L % 2 == 0 && CV_CPAD * CV_L % 2 == 0 && 4 * CV_L % 2 == 0, "whole dwords per sample and K-step");
+// the last fragment read: K-step 16, kg 3, row 13, dwords +0..3
+static_assert(((4 * (CV_STEPS - 1) + 3) * CV_L + CV_S * (CV_LOUT - 1)) / 2 + 3 < CH_LDS, "fragment reads stay inside");
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(2, 2)))
+void k_conv1d_pair_h(const uint32_t* __restrict__ x, const h8* __restrict__ frag, const float* __restrict__ bias,
+                     float* __restrict__ y, int batch) {
+  __shared__ uint32_t XS[2][CH_LDS];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // column tile of this wave
+  const int b0 = (int)((long long)blockIdx.x * batch / gridDim.x), b1 = (int)((long long)(blockIdx.x + 1) * batch / gridDim.x);
+  for (int i = CH_WORDS + (int)threadIdx.x; i < CH_LDS; i += 128) { XS[0][i] = 0u; XS[1][i] = 0u; }
+  const int h0 = w * CH_HALF, h1 = w == 0 ? CH_HALF : CH_WORDS;  // this wave's dword range of a sample
+  uint32_t pa[CH_PER_LANE], pb[CH_PER_LANE];
+  // unconditional, clamped loads, as k_conv1d_pair's
+  auto load = [&](uint32_t (&dst)[CH_PER_LANE], int bs) {
+    const uint32_t* src = x + (size_t)(bs < b1 ? bs : b1 - 1) * CH_WORDS;
+#pragma unroll
+    for (int k = 0; k < CH_PER_LANE; ++k) {
+      const int i = h0 + lane + 64 * k;
+      dst[k] = src[i < h1 ? i : h1 - 1];
+    }
+  };
+  if (b0 < b1) {
+    load(pa, b0);
+    load(pb, b0 + 1);
+  }
+  h8 bf[CV_STEPS][2];
+#pragma unroll
+  for (int s = 0; s < CV_STEPS; ++s)
+#pragma unroll
+    for (int hl = 0; hl < 2; ++hl) bf[s][hl] = frag[((s * 2 + w) * 2 + hl) * 64 + lane];
+  const float bo = bias[16 * w + (lane & 15)];
+  // the fragments and the bias retired before the loop (see k_conv1d_regs)
+#pragma unroll
+  for (int s = 0; s < CV_STEPS; ++s) asm volatile("" ::"v"(bf[s][0]), "v"(bf[s][1]));
+  asm volatile("" ::"v"(bo));
+  const int r = lane & 15, kg = lane >> 4;
+  const int rr = r < CV_LOUT ? r : CV_LOUT - 1;
+  const int f0 = kg * CV_L + CV_S * rr;           // the lane's first half within a K-step's 4 channel rows
+  const uint32_t sh = 16u * (uint32_t)(f0 & 1);   // odd: the fragment starts in the high half of its first dword
+  typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+  auto process = [&](uint32_t (&cur)[CH_PER_LANE], int bc, uint32_t* X) {
+#pragma unroll
+    for (int k = 0; k < CH_PER_LANE; ++k) {
+      const int i = h0 + lane + 64 * k;
+      if (i < h1) X[i] = cur[k];
+    }
+    load(cur, bc + 2);
+    __syncthreads();  // both halves staged (and, X being double-buffered, both waves done with the sample before last)
+    f4 acc0 = f4{0.0f, 0.0f, 0.0f, 0.0f}, acc1 = f4{0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int s = 0; s < CV_STEPS; ++s) {
+      const uint32_t* row = X + s * (4 * CV_L / 2) + (f0 >> 1);
+      uint32_t v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = row[j];
+      const u4 hv = {__builtin_amdgcn_alignbit(v[1], v[0], sh), __builtin_amdgcn_alignbit(v[2], v[1], sh),
+                     __builtin_amdgcn_alignbit(v[3], v[2], sh), 0u};  // taps 0..5; taps 6, 7 zero
+      const h8 ah = __builtin_bit_cast(h8, hv);
+      acc0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bf[s][0], acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bf[s][1], acc1, 0, 0, 0);
+    }
+    const int o = 16 * w + (lane & 15);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int l = 4 * kg + i < CV_LOUT ? 4 * kg + i : CV_LOUT - 1;  // rows 14, 15 = row 13's result, bit for bit
+      y[((size_t)bc * CV_LOUT + l) * CV_O + o] = acc0[i] + acc1[i] * (1.0f / CV_SPLIT) + bo;
+    }
+  };
+  for (int b = b0; b < b1; b += 2) {
+    process(pa, b, XS[0]);
+    if (b + 1 < b1) process(pb, b + 1, XS[1]);
+  }
+}
+
 // The PPO minibatch's actor observations rebuilt from the frame-history rollout storage (algo/rollout.py
 // _HistoryRows): row m is the window of frames k .. k + F - 1 of env n's sequence seq[n] ((F + T - 1) frames of `frame`
 // values, k = idx[m] / N, n = idx[m] % N), with the frames older than the env's latest reset at or before step k
@@ -471,6 +560,19 @@ __global__ __launch_bounds__(256) void k_gather_rows(GrFields F, const int64_t* 
   F.dst[f][(size_t)m * w + c] = F.src[f][(size_t)idx[m] * w + c];
 }
 
+// the current device's CU count (queried once per device), 0 on a runtime error
+int cv_cu_count() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  static int cu_count[64];
+  int cus = __atomic_load_n(&cu_count[dev], __ATOMIC_RELAXED);
+  if (cus <= 0) {
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 0;
+    __atomic_store_n(&cu_count[dev], cus, __ATOMIC_RELAXED);
+  }
+  return cus;
+}
+
 }  // namespace
 
 extern "C" {
@@ -524,14 +626,8 @@ int t1policy_conv1d_forward(const float* x, const float* wt, const float* bias, 
   if (batch == 0) return 0;
   if (!(channels == CV_C && length == CV_L && out_channels == CV_O && kernel == CV_K && stride == CV_S)) return 1;
   if ((reinterpret_cast<uintptr_t>(x) & 7u) != 0) return -1;  // float2 sample loads
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -2;
-  static int cu_count[64];  // per device, queried once
-  int cus = __atomic_load_n(&cu_count[dev], __ATOMIC_RELAXED);
-  if (cus <= 0) {
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return -2;
-    __atomic_store_n(&cu_count[dev], cus, __ATOMIC_RELAXED);
-  }
+  const int cus = cv_cu_count();
+  if (cus <= 0) return -2;
   // one workgroup per CU (its LDS), never more workgroups than the samples need
   const long long need = ((long long)batch + CV_WAVES - 1) / CV_WAVES;
   const int grid = (int)(need < cus ? need : cus);
@@ -558,14 +654,8 @@ int t1policy_conv1d_forward_packed(const float* x, const void* frag, const float
   if (!(channels == CV_C && length == CV_L && out_channels == CV_O && kernel == CV_K && stride == CV_S)) return 1;
   if ((reinterpret_cast<uintptr_t>(x) & 15u) != 0 || (reinterpret_cast<uintptr_t>(frag) & 15u) != 0) return -1;
   if ((long long)batch * (CV_C * CV_L * 4) > 0x7fffffffLL) return -1;  // 32-bit buffer offsets
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -2;
-  static int cu_count[64];
-  int cus = __atomic_load_n(&cu_count[dev], __ATOMIC_RELAXED);
-  if (cus <= 0) {
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return -2;
-    __atomic_store_n(&cu_count[dev], cus, __ATOMIC_RELAXED);
-  }
+  const int cus = cv_cu_count();
+  if (cus <= 0) return -2;
   // k_conv1d_pair (default): CP_PAIRS_PER_CU two-wave workgroups per CU; T1POLICY_CONV=regs: k_conv1d_regs, one
   // 4-wave workgroup per CU (A/B).  No workgroup without a sample.
   const char* kv = getenv("T1POLICY_CONV");
@@ -582,6 +672,25 @@ int t1policy_conv1d_forward_packed(const float* x, const void* frag, const float
     hipLaunchKernelGGL(k_conv1d_pair, dim3(grid), dim3(128), 0, (hipStream_t)stream, x,
                        reinterpret_cast<const h8*>(frag), bias, y, batch);
   }
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// forward_packed on an fp16 x: k_conv1d_pair_h only (T1POLICY_CONV=regs has no fp16 instance), k_conv1d_pair's grid rule
+int t1policy_conv1d_forward_packed_h(const void* x, const void* frag, const float* bias, float* y, int batch,
+                                     int channels, int length, int out_channels, int kernel, int stride, void* stream) {
+  if (!x || !frag || !bias || !y || batch < 0) return -1;
+  if (batch == 0) return 0;
+  if (!(channels == CV_C && length == CV_L && out_channels == CV_O && kernel == CV_K && stride == CV_S)) return 1;
+  if ((reinterpret_cast<uintptr_t>(x) & 3u) != 0 || (reinterpret_cast<uintptr_t>(frag) & 15u) != 0) return -1;  // dword sample loads
+  if ((long long)batch * (CV_C * CV_L * 2) > 0x7fffffffLL) return -1;  // 32-bit buffer offsets
+  const int cus = cv_cu_count();
+  if (cus <= 0) return -2;
+  const char* pv = getenv("T1POLICY_CONV_PAIRS");  // pairs per CU (A/B), as forward_packed
+  const int pairs = pv && atoi(pv) >= 1 && atoi(pv) <= 6 ? atoi(pv) : CP_PAIRS_PER_CU;
+  const long long slots = (long long)cus * pairs;
+  const int grid = (int)(batch < slots ? batch : slots);
+  hipLaunchKernelGGL(k_conv1d_pair_h, dim3(grid), dim3(128), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(x),
+                     reinterpret_cast<const h8*>(frag), bias, y, batch);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -33,6 +33,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -657,9 +658,12 @@ struct PhOut64 {  // the global outputs and the workgroup's envs
 };
 
 // staging as ph_stage, for both env tiles: element j of lane (r, h) of step s, tile et = src[env0 + 32 et + r][col0 +
-// 16 s + 8 h + j]
-template <bool RELU>
-__device__ __forceinline__ void ph6_stage(Frag2* dst, int steps, const float* __restrict__ src, long long stride,
+// 16 s + 8 h + j].  T: the source's element type.  An fp16 source (the env's fp16 histories) is its own hi part and its
+// lo part is exactly 0 -- what split8 makes of the widened value, so the staged fragments are the fp32 path's on
+// obs.float() bit for bit (finite values) -- read by 16-bit loads: its rows are 2-byte aligned only (an obs row's short
+// history starts at half 2867 of a 6204-byte row, a critic row is 438 B).
+template <bool RELU, typename T>
+__device__ __forceinline__ void ph6_stage(Frag2* dst, int steps, const T* __restrict__ src, long long stride,
                                           int col0, int len, int env0, int batch, int wave, int lane) {
   const int h = lane >> 5;
   for (int s = wave; s < steps; s += PH_WAVES) {
@@ -667,18 +671,30 @@ __device__ __forceinline__ void ph6_stage(Frag2* dst, int steps, const float* __
     for (int et = 0; et < 2; ++et) {
       const int env = env0 + 32 * et + (lane & 31);
       const bool live = env < batch;
-      const float* row = src + (long long)(live ? env : batch - 1) * stride + col0;
-      float v[8];
+      const T* row = src + (long long)(live ? env : batch - 1) * stride + col0;
+      if constexpr (std::is_same<T, _Float16>::value) {
+        static_assert(!RELU, "the fp16 sources are staged as they are");
+        h8 hi;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int c = 16 * s + 8 * h + j;
-        const float x = (live && c < len) ? row[c] : 0.0f;
-        v[j] = RELU ? (x > 0.0f ? x : 0.0f) : x;
+        for (int j = 0; j < 8; ++j) {
+          const int c = 16 * s + 8 * h + j;
+          hi[j] = (live && c < len) ? row[c] : (_Float16)0.0f;
+        }
+        dst[s][et][0][lane] = hi;
+        dst[s][et][1][lane] = h8{0, 0, 0, 0, 0, 0, 0, 0};
+      } else {
+        float v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int c = 16 * s + 8 * h + j;
+          const float x = (live && c < len) ? row[c] : 0.0f;
+          v[j] = RELU ? (x > 0.0f ? x : 0.0f) : x;
+        }
+        h8 hi, lo;
+        split8(v, hi, lo);
+        dst[s][et][0][lane] = hi;
+        dst[s][et][1][lane] = lo;
       }
-      h8 hi, lo;
-      split8(v, hi, lo);
-      dst[s][et][0][lane] = hi;
-      dst[s][et][1][lane] = lo;
     }
   }
 }
@@ -789,9 +805,11 @@ __device__ __forceinline__ void ph6_call(const h8* __restrict__ frag, const Frag
 template <int L, int KB, int KE, int TB = 0> using R6 = P6Ring<L, KB, KE, TB>;
 template <int L> using R6F = P6Ring<L, 0, PH_L[L].ks, 0>;  // a whole layer
 
+// TO: the element type of obs and cobs (float, or _Float16: t1policy_heads_forward_h); y1 is fp32 either way
+template <typename TO>
 __global__ __launch_bounds__(64 * PH_WAVES) __attribute__((amdgpu_waves_per_eu(PH_WAVES / 4, PH_WAVES / 4)))
-void k_heads64(const h8* __restrict__ frag, const float* __restrict__ y1, const float* __restrict__ obs, int obs_cols,
-               const float* __restrict__ cobs, int cobs_cols, PhOut64 G, int batch) {
+void k_heads64(const h8* __restrict__ frag, const float* __restrict__ y1, const TO* __restrict__ obs, int obs_cols,
+               const TO* __restrict__ cobs, int cobs_cols, PhOut64 G, int batch) {
   __shared__ Heads64Lds S;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -939,7 +957,7 @@ int t1policy_heads_forward(const uint64_t* params, const int* dims, const void* 
   if (!(hv && hv[0] == '0')) {
     const PhOut64 G{eps, P.std, mean, actions, sigma, logp, value, 0, batch};
     const int tiles = (batch + 63) / 64;
-    hipLaunchKernelGGL(k_heads64, dim3(16 * ((tiles + 7) / 8)), dim3(64 * PH_WAVES), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(k_heads64<float>, dim3(16 * ((tiles + 7) / 8)), dim3(64 * PH_WAVES), 0, (hipStream_t)stream,
                        reinterpret_cast<const h8*>(frag), y1, obs, obs_cols, critic_obs, critic_cols, G, batch);
     return hipGetLastError() == hipSuccess ? 0 : -2;
   }
@@ -954,6 +972,31 @@ int t1policy_heads_forward(const uint64_t* params, const int* dims, const void* 
   hipLaunchKernelGGL(k_heads, dim3(grid), dim3(64 * PH_WAVES), 0, (hipStream_t)stream, P,
                      reinterpret_cast<const h8*>(frag), y1, obs, obs_cols, critic_obs, critic_cols, G, batch,
                      xcd_split);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// heads_forward on fp16 obs / critic_obs: k_heads64<_Float16> (the 32-env k_heads has no fp16 instance: 1)
+int t1policy_heads_forward_h(const uint64_t* params, const int* dims, const void* frag, const float* y1,
+                             const void* obs, int obs_cols, const void* critic_obs, int critic_cols, const float* eps,
+                             float* mean, float* actions, float* sigma, float* logp, float* value, int batch,
+                             void* stream) {
+  if (!params || !dims || !frag || !y1 || !obs || !critic_obs || !eps || !mean || !actions || !sigma || !logp ||
+      !value || batch < 0)
+    return -1;
+  if (!ph_dims_match(dims)) return 1;
+  if (obs_cols < PH_OBS_SHORT || critic_cols != PH_CRITIC) return 1;
+  if (batch == 0) return 0;
+  if ((reinterpret_cast<uintptr_t>(frag) & 15u) != 0) return -1;
+  if (((reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(critic_obs)) & 1u) != 0) return -1;
+  PhParams P;
+  if (!ph_params(params, P)) return -1;
+  const char* hv = getenv("T1POLICY_HEADS64");
+  if (hv && hv[0] == '0') return 1;
+  const PhOut64 G{eps, P.std, mean, actions, sigma, logp, value, 0, batch};
+  const int tiles = (batch + 63) / 64;
+  hipLaunchKernelGGL(k_heads64<_Float16>, dim3(16 * ((tiles + 7) / 8)), dim3(64 * PH_WAVES), 0, (hipStream_t)stream,
+                     reinterpret_cast<const h8*>(frag), y1, reinterpret_cast<const _Float16*>(obs), obs_cols,
+                     reinterpret_cast<const _Float16*>(critic_obs), critic_cols, G, batch);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

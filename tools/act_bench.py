@@ -1,7 +1,10 @@
 """Dev probe: the rollout's act() (DHPPO.act: policy sample, value, log-prob as one replayed HIP graph) at N envs on
 random observations, fused HIP heads vs torch's layers (T1_FUSED_ACT is read at import; --torch flips it here).
 
-    python tools/act_bench.py [--num-envs 8192] [--iters 200] [--torch]
+    python tools/act_bench.py [--num-envs 8192] [--iters 200] [--torch] [--obs-dtype fp16]
+
+--obs-dtype fp16: the observations rounded to fp16 and passed as fp16 tensors, as an env with cfg.env.state_dtype =
+"fp16" returns them (BASELINE config 5).
 
 Prints one JSON line: wall ms per act() (graph replays back to back, one sync at the end), and the heads kernel's own
 duration from HIP events around the fused call when it runs eagerly.
@@ -22,6 +25,7 @@ def main():
     p.add_argument("--num-envs", type=int, default=8192)
     p.add_argument("--iters", type=int, default=200)
     p.add_argument("--torch", action="store_true")
+    p.add_argument("--obs-dtype", choices=["fp32", "fp16"], default="fp32")
     a = p.parse_args()
     from ti5_isaacgym_amd import task_registry
     from ti5_isaacgym_amd.algo import dh_update
@@ -37,7 +41,9 @@ def main():
     n = a.num_envs
     obs = torch.randn(n, 66 * 47, device=dev).clamp(-18, 18)
     cobs = torch.randn(n, 219, device=dev)
-    out = {"num_envs": n, "path": "torch" if a.torch else "fused"}
+    if a.obs_dtype == "fp16":
+        obs, cobs = obs.half(), cobs.half()
+    out = {"num_envs": n, "path": "torch" if a.torch else "fused", "obs_dtype": a.obs_dtype}
     with torch.inference_mode():
         for _ in range(5):
             alg.act(obs, cobs)
