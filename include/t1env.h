@@ -101,6 +101,13 @@ typedef struct t1env_config {
   int32_t lag_range[2], dof_lag_range[2], imu_lag_range[2];
   float torque_mult_range[2], motor_offset_range[2], kp_mult_range[2], kd_mult_range[2];
   float coulomb_range[2], viscous_range[2], armature_range[T1_ND][2];
+  /* 1: domain_rand.randomize_joint_armature_each_joint = False -- one armature draw per env (the draw of joint 0)
+   * used for all 12 joints (legged_robot.py:781-783, 936-937); armature_range[j] then all hold joint_armature_range */
+  int32_t armature_shared;
+  /* 1: domain_rand.add_dof_lag / add_imu_lag = False -- no lag ring: the observation reads the joint / base state
+   * itself, also for an env reset this step (its new state, where a ring would read the zeros of its reset;
+   * t1_dh_stand_env.py:432-434, 446-448).  The lag range is then [0, 0]. */
+  int32_t dof_lag_off, imu_lag_off;
   float reset_dof_range;        /* +-0.1 */
   int32_t terrain_curriculum;   /* mesh in (heightfield, trimesh) and curriculum */
   float platform, env_length;   /* terrain platform [m], terrain_length [m] */

@@ -85,6 +85,63 @@ HEIGHT_X = [round(-0.8 + 0.1 * i, 1) for i in range(17)]   # legged_robot_config
 HEIGHT_Y = [round(-0.5 + 0.1 * i, 1) for i in range(11)]   # legged_robot_config.py:30
 NUM_HEIGHT = len(HEIGHT_X) * len(HEIGHT_Y)                  # 187 (legged_robot_config.py:36)
 HEIGHT_OBS_SCALE = 5.0    # obs_scales.height_measurements (t1_dh_stand_config.py:424)
+NOISE_SCALES = dict(dof_pos=0.02, dof_vel=1.5, ang_vel=0.2, quat=0.1)   # :115-122
+GAIT_KINDS = ("walk_omnidirectional", "stand", "walk_sagittal", "walk_lateral", "rotate")
+GAIT_TIME_RANGE = {"walk_sagittal": (2, 6), "walk_lateral": (2, 6), "rotate": (2, 3), "stand": (2, 3),
+                   "walk_omnidirectional": (4, 6)}                      # :331-335
+
+
+def default_cfg():
+    """Every cfg value the oracle reads, as a flat dict: dotted path (the reference's attribute path below the env cfg)
+    -> the DHT1StandCfg default, i.e. the module constants above.  T1Oracle(cfg_overrides=...) replaces entries; a path
+    that is not listed raises, so a scenario cannot set a knob the oracle would ignore.  The terrain.* entries describe
+    the terrain the caller passes in (`terrain`, `measure_heights`, `terrain_curriculum`) and are accepted only."""
+    c = {
+        "control.decimation": DECIMATION, "control.action_scale": ACTION_SCALE, "env.episode_length_s": EPISODE_S,
+        "normalization.clip_actions": CLIP_ACTIONS, "normalization.clip_observations": CLIP_OBS,
+        "noise.add_noise": True, "noise.noise_level": NOISE_LEVEL,
+        "commands.gait": list(GAIT), "commands.stand_com_threshold": STAND_THRESH,
+        "commands.ranges.lin_vel_x": [-0.5, 0.5], "commands.ranges.lin_vel_y": [-0.5, 0.5],
+        "commands.ranges.ang_vel_yaw": [-0.5, 0.5],
+        "rewards.only_positive_rewards": True, "rewards.tracking_sigma": 5, "rewards.max_contact_force": 500,
+        "rewards.base_height_target": 0.965, "rewards.foot_min_dist": 0.15, "rewards.foot_max_dist": 0.45,
+        "rewards.knee_min_dist": 0.12, "rewards.knee_max_dist": 0.35, "rewards.target_feet_height": 0.02,
+        "rewards.target_feet_height_max": 0.08, "rewards.cycle_time": CYCLE_TIME, "rewards.target_joint_pos_scale": 0.3,
+        "domain_rand.randomize_friction": True, "domain_rand.friction_range": [0.2, 1.3],
+        "domain_rand.restitution_range": [0.0, 0.4],
+        "domain_rand.randomize_base_mass": True, "domain_rand.added_mass_range": [-2.5, 2.5],
+        "domain_rand.randomize_com": True, "domain_rand.com_displacement_range": [[-0.05, 0.05]] * 3,
+        "domain_rand.randomize_link_mass": True, "domain_rand.added_link_mass_range": [0.9, 1.1],
+        "domain_rand.randomize_gains": True, "domain_rand.stiffness_multiplier_range": [0.8, 1.2],
+        "domain_rand.damping_multiplier_range": [0.8, 1.2],
+        "domain_rand.randomize_torque": True, "domain_rand.torque_multiplier_range": [0.8, 1.2],
+        "domain_rand.randomize_motor_offset": True, "domain_rand.motor_offset_range": [-0.035, 0.035],
+        "domain_rand.randomize_coulomb_friction": True, "domain_rand.joint_coulomb_range": [0.1, 1.0],
+        "domain_rand.joint_viscous_range": [0.1, 0.9],
+        "domain_rand.randomize_joint_armature": True, "domain_rand.randomize_joint_armature_each_joint": True,
+        "domain_rand.joint_armature_range": [0.001, 0.05],
+        "domain_rand.add_lag": True, "domain_rand.randomize_lag_timesteps": True,
+        "domain_rand.lag_timesteps_range": [0, 30],
+        "domain_rand.add_dof_lag": True, "domain_rand.randomize_dof_lag_timesteps": True,
+        "domain_rand.dof_lag_timesteps_range": [0, 30],
+        "domain_rand.add_imu_lag": True, "domain_rand.randomize_imu_lag_timesteps": True,
+        "domain_rand.imu_lag_timesteps_range": [0, 10],
+        "domain_rand.ext_force_max_x": EXT_FORCE_MAX[0], "domain_rand.ext_force_max_y": EXT_FORCE_MAX[1],
+        "domain_rand.ext_force_max_z": EXT_FORCE_MAX[2],
+        "domain_rand.push_robots": False, "domain_rand.push_interval_s": PUSH_INTERVAL_S,
+        "terrain.num_rows": None, "terrain.num_cols": None, "terrain.border_size": None, "terrain.curriculum": None,
+    }
+    for k, v in OBS_SCALES.items():
+        c["normalization.obs_scales." + k] = v
+    for k, v in NOISE_SCALES.items():
+        c["noise.noise_scales." + k] = v
+    for k, v in GAIT_TIME_RANGE.items():
+        c["commands.gait_time_range." + k] = list(v)
+    for k, v in REWARD_SCALES.items():
+        c["rewards.scales." + k] = v
+    for j, r in enumerate(ARMATURE_RANGE):
+        c[f"domain_rand.joint_{j + 1}_armature_range"] = list(r)
+    return c
 
 
 def euler_xyz(q):
@@ -154,43 +211,85 @@ class T1Oracle:
     (root (N,13), dof (N,12,2), rigid (N,13,13), contact (N,13,3)) after global substep g."""
 
     def __init__(self, num_envs, seed=5, mesh_type="plane", terrain=None, env_offset=0, reduce_fn=None,
-                 measure_heights=False, push_robots=False, push_interval_s=PUSH_INTERVAL_S, terrain_curriculum=True):
+                 measure_heights=False, push_robots=False, push_interval_s=PUSH_INTERVAL_S, terrain_curriculum=True,
+                 cfg_overrides=None):
         """reduce_fn: sharded runs only -- (sum, count) -> (sum, count) over all ranks, so the command
         curriculum sees the same mean as an unsharded run.  measure_heights: the height scan
         (inactive in DHT1StandCfg): 187 heights appended to every critic frame (260 per frame).  push_robots /
         push_interval_s: domain_rand.push_robots (off in DHT1StandCfg, on in BASELINE config 5).  terrain_curriculum:
         cfg.terrain.curriculum (on in DHT1StandCfg; off: levels drawn over every row, no level updates, start xy
-        within terrain_length / 2, legged_robot.py:1103-1108, 1487)."""
+        within terrain_length / 2, legged_robot.py:1103-1108, 1487).  cfg_overrides: {dotted cfg path: value} over
+        default_cfg() (the non-default scenarios of tests/golden/gen_golden.py); None leaves every value at the
+        DHT1StandCfg default."""
         N = num_envs
+        cfg = default_cfg()
+        for k, v in (cfg_overrides or {}).items():
+            if k not in cfg:
+                raise KeyError(f"T1Oracle: cfg path {k!r} is not one the oracle reads (default_cfg)")
+            cfg[k] = v
+        self.cfg = cfg
+        dr = lambda k: cfg["domain_rand." + k]   # noqa: E731
+        self.decimation = int(cfg["control.decimation"])
+        self.dt = self.decimation * SIM_DT                                          # legged_robot.py:96
+        self.episode_s = cfg["env.episode_length_s"]
+        self.max_episode_length = float(np.ceil(self.episode_s / self.dt))         # legged_robot.py:109
+        self.ext_interval = float(np.ceil(4 / self.dt))                             # legged_robot.py:113
+        self.gait = tuple(cfg["commands.gait"])
+        for g in self.gait:
+            if g not in GAIT_KINDS:
+                raise KeyError(f"T1Oracle: unknown gait {g!r}")
+        self.stand_thresh = cfg["commands.stand_com_threshold"]
+        self.obs_scales = {k: cfg["normalization.obs_scales." + k] for k in OBS_SCALES}
+        self.ext_force_max = tuple(dr("ext_force_max_" + a) for a in "xyz")
+        if dr("push_robots"):
+            push_robots, push_interval_s = True, dr("push_interval_s")
         self.N, self.seed, self.env_offset = N, int(seed), int(env_offset)
         self.reduce_fn = reduce_fn
         self.ids = np.arange(N, dtype=np.int64) + env_offset
         self.mesh_type = mesh_type
         self.custom_origins = mesh_type in ("heightfield", "trimesh")   # legged_robot.py:1481-1482
         self.curriculum = self.custom_origins and bool(terrain_curriculum)  # legged_robot.py:104-105
-        self.command_ranges = dict(lin_vel_x=[-0.5, 0.5], lin_vel_y=[-0.5, 0.5], ang_vel_yaw=[-0.5, 0.5])
-        self.reward_scales = {k: v * DT for k, v in REWARD_SCALES.items()}   # legged_robot.py:357-364
+        self.command_ranges = {k: list(cfg["commands.ranges." + k]) for k in ("lin_vel_x", "lin_vel_y", "ang_vel_yaw")}
+        # _prepare_reward_function (legged_robot.py:351-384): zero scales are dropped -- no reward function, no
+        # episode sum, no extras["episode"] key -- the others multiplied by dt
+        self.reward_scales = {k: cfg["rewards.scales." + k] * self.dt for k in REWARD_NAMES
+                              if cfg["rewards.scales." + k] != 0}
+        self.reward_names = [k for k in REWARD_NAMES if k in self.reward_scales]
+        ns, os_ = {k: cfg["noise.noise_scales." + k] for k in NOISE_SCALES}, self.obs_scales
         self.noise_vec = np.zeros(NUM_SINGLE_OBS, f32)                       # t1_dh_stand_env.py:326-357
-        self.noise_vec[5:17] = f32(0.02 * OBS_SCALES["dof_pos"])
-        self.noise_vec[17:29] = f32(1.5 * OBS_SCALES["dof_vel"])
-        self.noise_vec[41:44] = f32(0.2 * OBS_SCALES["ang_vel"])
-        self.noise_vec[44:47] = f32(0.1 * OBS_SCALES["quat"])
+        self.noise_vec[5:17] = f32(ns["dof_pos"] * os_["dof_pos"])
+        self.noise_vec[17:29] = f32(ns["dof_vel"] * os_["dof_vel"])
+        self.noise_vec[41:44] = f32(ns["ang_vel"] * os_["ang_vel"])
+        self.noise_vec[44:47] = f32(ns["quat"] * os_["quat"])
         self.common_step_counter = 0
         self._key_salt = 0         # R.BETWEEN_STEP_SALT while reset_idx runs between steps
         self.substep_counter = 0
         self.push_robots = bool(push_robots)
-        self.push_interval = float(np.ceil(push_interval_s / DT))          # legged_robot.py:112
-        # creation-time DR (legged_robot.py:692-730, 786-824, 852-885)
-        self.payload = R.rand_float(-2.5, 2.5, seed, self.ids, 0, R.SLOT_PAYLOAD)
+        self.push_interval = float(np.ceil(push_interval_s / self.dt))     # legged_robot.py:112
+        # creation-time DR (legged_robot.py:692-730, 786-824, 852-885); a switched-off randomisation leaves the
+        # nominal value (env_frictions and the restitution stay 0: the asset's shape properties are not reported)
+        self.payload = np.zeros(N, f32)
+        if dr("randomize_base_mass"):
+            lo, hi = dr("added_mass_range")
+            self.payload = R.rand_float(lo, hi, seed, self.ids, 0, R.SLOT_PAYLOAD)
         self.body_mass = (f32(BASE_MASS) + self.payload).astype(f32)
-        bucket = R.randint(0, 256, seed, self.ids, 0, R.SLOT_FRICTION_BUCKET)
-        fr_b = R.rand_float(0.2, 1.3, seed, np.arange(256), 0, R.SLOT_FRICTION_VALUE)
-        re_b = R.rand_float(0.0, 0.4, seed, np.arange(256), 0, R.SLOT_RESTITUTION_VALUE)
-        self.friction = fr_b[bucket]
-        self.restitution = re_b[bucket]
-        self.link_mass_scale = np.stack([R.rand_float(0.9, 1.1, seed, self.ids, 0, R.SLOT_LINK_MASS + b)
-                                         for b in range(12)], 1)
-        self.com_disp = np.stack([R.rand_float(-0.05, 0.05, seed, self.ids, 0, R.SLOT_COM + k) for k in range(3)], 1)
+        self.friction, self.restitution = np.zeros(N, f32), np.zeros(N, f32)
+        if dr("randomize_friction"):
+            bucket = R.randint(0, 256, seed, self.ids, 0, R.SLOT_FRICTION_BUCKET)
+            fr_b = R.rand_float(*dr("friction_range"), seed, np.arange(256), 0, R.SLOT_FRICTION_VALUE)
+            re_b = R.rand_float(*dr("restitution_range"), seed, np.arange(256), 0, R.SLOT_RESTITUTION_VALUE)
+            self.friction = fr_b[bucket]
+            self.restitution = re_b[bucket]
+        self.link_mass_scale = np.ones((N, 12), f32)
+        if dr("randomize_link_mass"):
+            lo, hi = dr("added_link_mass_range")
+            self.link_mass_scale = np.stack([R.rand_float(lo, hi, seed, self.ids, 0, R.SLOT_LINK_MASS + b)
+                                             for b in range(12)], 1)
+        self.com_disp = np.zeros((N, 3), f32)
+        if dr("randomize_com"):
+            cr = dr("com_displacement_range")
+            self.com_disp = np.stack([R.rand_float(cr[k][0], cr[k][1], seed, self.ids, 0, R.SLOT_COM + k)
+                                      for k in range(3)], 1)
         # terrain origins (legged_robot.py:1477-1512)
         self.env_origins = np.zeros((N, 3), f32)
         if self.custom_origins:
@@ -263,10 +362,25 @@ class T1Oracle:
         self.lag_buffer = z(N, 12, 31)
         self.dof_lag_buffer = z(N, 24, 31)
         self.imu_lag_buffer = z(N, 6, 11)
-        self.lag_timestep = R.randint(0, 31, seed, self.ids, 0, R.SLOT_LAG_ACTION)
-        self.dof_lag_timestep = R.randint(0, 31, seed, self.ids, 0, R.SLOT_LAG_DOF)
-        self.imu_lag_timestep = R.randint(0, 11, seed, self.ids, 0, R.SLOT_LAG_IMU)
-        self.episode_sums = {k: z(N) for k in REWARD_NAMES}
+        # lag lengths (legged_robot.py:270-321, 604-633): drawn in [lo, hi], or hi when not randomised; a lag that
+        # is switched off reads the newest sample (length 0; the dof / imu observation then reads the state itself)
+        self.lag_ranges = {}
+        for name, flag, rnd, rng, cap in (("lag", "add_lag", "randomize_lag_timesteps", "lag_timesteps_range", 30),
+                                          ("dof", "add_dof_lag", "randomize_dof_lag_timesteps",
+                                           "dof_lag_timesteps_range", 30),
+                                          ("imu", "add_imu_lag", "randomize_imu_lag_timesteps",
+                                           "imu_lag_timesteps_range", 10)):
+            lo, hi = (int(x) for x in dr(rng))
+            assert 0 <= lo <= hi <= cap, (rng, lo, hi)
+            self.lag_ranges[name] = (0, 0) if not dr(flag) else (lo, hi) if dr(rnd) else (hi, hi)
+        self.add_dof_lag, self.add_imu_lag = bool(dr("add_dof_lag")), bool(dr("add_imu_lag"))
+        self.lag_timestep = R.randint(self.lag_ranges["lag"][0], self.lag_ranges["lag"][1] + 1, seed, self.ids, 0,
+                                      R.SLOT_LAG_ACTION)
+        self.dof_lag_timestep = R.randint(self.lag_ranges["dof"][0], self.lag_ranges["dof"][1] + 1, seed, self.ids, 0,
+                                          R.SLOT_LAG_DOF)
+        self.imu_lag_timestep = R.randint(self.lag_ranges["imu"][0], self.lag_ranges["imu"][1] + 1, seed, self.ids, 0,
+                                          R.SLOT_LAG_IMU)
+        self.episode_sums = {k: z(N) for k in self.reward_names}
         # randomize_dof_props at creation runs before p_gains exist -> randomized gains are 0
         self.kp_r, self.kd_r = z(N, 12), z(N, 12)
         self.motor_offsets, self.coulomb, self.viscous = z(N, 12), z(N, 12), z(N, 12)
@@ -289,9 +403,10 @@ class T1Oracle:
     # ---------------------------------------------------------------- step
     def step(self, actions, physics):
         """legged_robot.py:387-448"""
-        self.actions = np.clip(actions.astype(f32), -CLIP_ACTIONS, CLIP_ACTIONS)
+        clip_actions = self.cfg["normalization.clip_actions"]
+        self.actions = np.clip(actions.astype(f32), -clip_actions, clip_actions)
         self.torque_log = []
-        for sub in range(DECIMATION):
+        for sub in range(self.decimation):
             self.torques = self._compute_torques(self.actions, sub)
             self.torque_log.append(self.torques.copy())
             root, dof, rigid, contact = physics(self.substep_counter, self.torques, self)
@@ -308,8 +423,9 @@ class T1Oracle:
             self.imu_lag_buffer[:, :, 1:] = self.imu_lag_buffer[:, :, :10].copy()
             self.imu_lag_buffer[:, :, 0] = np.concatenate([self.base_ang_vel, self.base_euler_xyz], 1)
         self.post_physics_step()
-        self.obs_buf = np.clip(self.obs_buf, -CLIP_OBS, CLIP_OBS)
-        self.priv_buf = np.clip(self.priv_buf, -CLIP_OBS, CLIP_OBS)
+        clip_obs = self.cfg["normalization.clip_observations"]
+        self.obs_buf = np.clip(self.obs_buf, -clip_obs, clip_obs)
+        self.priv_buf = np.clip(self.priv_buf, -clip_obs, clip_obs)
         return self.obs_buf, self.priv_buf, self.rew_buf, self.reset_buf, self.extras
 
     def reset(self, physics):
@@ -321,15 +437,18 @@ class T1Oracle:
 
     def _compute_torques(self, actions, sub):
         """legged_robot.py:1019-1074"""
-        a_s = (actions * f32(ACTION_SCALE)).astype(f32)
+        a_s = (actions * f32(self.cfg["control.action_scale"])).astype(f32)
         self.lag_buffer[:, :, 1:] = self.lag_buffer[:, :, :30].copy()
         self.lag_buffer[:, :, 0] = a_s
         lagged = self.lag_buffer[np.arange(self.N), :, self.lag_timestep]
-        tq = self.kp_r * (lagged + Q0 - self.dof[:, :, 0] + self.motor_offsets) - self.kd_r * self.dof[:, :, 1] \
-            - self.viscous * self.dof[:, :, 1] - self.coulomb * np.sign(self.dof[:, :, 1])
-        self.torque_multi = np.stack([self._rf(0.8, 1.2, np.arange(self.N), R.SLOT_TORQUE_MULT + sub * 12 + j)
-                                      for j in range(12)], 1)
-        tq = (tq * self.torque_multi).astype(f32)
+        tq = self.kp_r * (lagged + Q0 - self.dof[:, :, 0] + self.motor_offsets) - self.kd_r * self.dof[:, :, 1]
+        if self.cfg["domain_rand.randomize_coulomb_friction"]:
+            tq = tq - self.viscous * self.dof[:, :, 1] - self.coulomb * np.sign(self.dof[:, :, 1])
+        if self.cfg["domain_rand.randomize_torque"]:
+            lo, hi = self.cfg["domain_rand.torque_multiplier_range"]
+            self.torque_multi = np.stack([self._rf(lo, hi, np.arange(self.N), R.SLOT_TORQUE_MULT + sub * 12 + j)
+                                          for j in range(12)], 1)
+            tq = (tq * self.torque_multi).astype(f32)
         return np.clip(tq, -TORQUE_LIMITS, TORQUE_LIMITS).astype(f32)
 
     def post_physics_step(self):
@@ -355,20 +474,22 @@ class T1Oracle:
 
     # ---------------------------------------------------------------- callback (t1:179-215)
     def _stand(self):
-        return _norm(self.commands[:, :3], 1) <= STAND_THRESH
+        return _norm(self.commands[:, :3], 1) <= self.stand_thresh
 
     def _resample_commands(self):
-        """t1_dh_stand_env.py:126-136 (+ walk_omnidirectional 170-177, stand 138-144)"""
-        for i, name in enumerate(GAIT):
+        """t1_dh_stand_env.py:126-136 (+ stand 138-144, walk_sagittal 146-152, walk_lateral 154-160, rotate 162-168,
+        walk_omnidirectional 170-177; heading_command off): a kind sets its own components and zeroes the others"""
+        for i, name in enumerate(self.gait):
             ids = np.nonzero(self.episode_length_buf == self.gait_time[:, i])[0]
             if len(ids) == 0:
                 continue
-            if name == "stand":
-                self.commands[ids, 0:3] = 0.0
-            else:
-                cr = self.command_ranges
+            cr = self.command_ranges
+            self.commands[ids, 0:3] = 0.0
+            if name in ("walk_omnidirectional", "walk_sagittal"):
                 self.commands[ids, 0] = self._rf(cr["lin_vel_x"][0], cr["lin_vel_x"][1], ids, R.SLOT_CMD_X)
+            if name in ("walk_omnidirectional", "walk_lateral"):
                 self.commands[ids, 1] = self._rf(cr["lin_vel_y"][0], cr["lin_vel_y"][1], ids, R.SLOT_CMD_Y)
+            if name in ("walk_omnidirectional", "rotate"):
                 self.commands[ids, 2] = self._rf(cr["ang_vel_yaw"][0], cr["ang_vel_yaw"][1], ids, R.SLOT_CMD_YAW)
 
     def _get_heights(self):
@@ -386,15 +507,15 @@ class T1Oracle:
             self.measured_heights = self._get_heights()
         if self.push_robots:                                     # t1_dh_stand_env.py:193-202
             i = min(int(self.common_step_counter / PUSH_UPDATE_STEP), len(PUSH_DURATION) - 1)
-            if self.common_step_counter % self.push_interval <= PUSH_DURATION[i] / DT:
+            if self.common_step_counter % self.push_interval <= PUSH_DURATION[i] / self.dt:
                 self._push_robots()
             else:
                 self.rand_push_force[:] = 0
                 self.rand_push_torque[:] = 0
         i = int(self.common_step_counter / ADD_UPDATE_STEP)
         i = min(i, len(ADD_DURATION) - 1)
-        duration = ADD_DURATION[i] / DT
-        if self.common_step_counter % EXT_INTERVAL <= duration:
+        duration = ADD_DURATION[i] / self.dt
+        if self.common_step_counter % self.ext_interval <= duration:
             self._add_ext_force()
         else:
             self.ext_forces[:] = 0
@@ -420,9 +541,10 @@ class T1Oracle:
         allids = np.arange(self.N)
         apply = np.zeros((self.N, 13, 3), f32)
         if self.is_first_add_force:
-            fx = self._rf(-EXT_FORCE_MAX[0] / 2, EXT_FORCE_MAX[0], allids, R.SLOT_EXT_FORCE + 0)
-            fy = self._rf(-EXT_FORCE_MAX[1], EXT_FORCE_MAX[1], allids, R.SLOT_EXT_FORCE + 1)
-            fz = self._rf(-EXT_FORCE_MAX[2], EXT_FORCE_MAX[2], allids, R.SLOT_EXT_FORCE + 2)
+            fm = self.ext_force_max
+            fx = self._rf(-fm[0] / 2, fm[0], allids, R.SLOT_EXT_FORCE + 0)
+            fy = self._rf(-fm[1], fm[1], allids, R.SLOT_EXT_FORCE + 1)
+            fz = self._rf(-fm[2], fm[2], allids, R.SLOT_EXT_FORCE + 2)
             self.ext_forces = np.stack([fx, fy, fz], 1)
             self.ext_torques = np.stack([self._rf(-EXT_TORQUE_MAX, EXT_TORQUE_MAX, allids, R.SLOT_EXT_TORQUE + k)
                                          for k in range(3)], 1)
@@ -436,14 +558,14 @@ class T1Oracle:
     def _check_termination(self):
         """legged_robot.py:509-517"""
         self.reset_buf = np.any(_norm(self.contact[:, [BASE], :], -1) > 1, axis=1)
-        self.time_out_buf = self.episode_length_buf > MAX_EPISODE_LEN
+        self.time_out_buf = self.episode_length_buf > self.max_episode_length
         self.reset_buf |= self.time_out_buf
 
     # ---------------------------------------------------------------- phase helpers (t1:80-107, 250-274)
     def _get_phase(self):
         stand = self._stand()
         self.phase_length_buf[stand] = 0
-        ph = (self.phase_length_buf.astype(f32) * f32(DT)) / f32(CYCLE_TIME)
+        ph = (self.phase_length_buf.astype(f32) * f32(self.dt)) / f32(self.cfg["rewards.cycle_time"])
         ph = (ph - np.floor(ph)).astype(f32)
         return ((ph + self.gait_start) * (~stand)).astype(f32)
 
@@ -459,28 +581,30 @@ class T1Oracle:
         s = np.sin(f32(2 * PI) * self._get_phase()).astype(f32)
         sl, sr = s.copy(), s.copy()
         ref = np.zeros((self.N, 12), f32)
+        s1 = self.cfg["rewards.target_joint_pos_scale"]
+        s1, s2 = f32(s1), f32(2 * s1)
         sl[sl > 0] = 0
-        ref[:, 2] = sl * f32(0.3)
-        ref[:, 3] = -sl * f32(0.6)
-        ref[:, 4] = sl * f32(0.3)
+        ref[:, 2] = sl * s1
+        ref[:, 3] = -sl * s2
+        ref[:, 4] = sl * s1
         sr[sr < 0] = 0
-        ref[:, 8] = -sr * f32(0.3)
-        ref[:, 9] = sr * f32(0.6)
-        ref[:, 10] = -sr * f32(0.3)
+        ref[:, 8] = -sr * s1
+        ref[:, 9] = sr * s2
+        ref[:, 10] = -sr * s1
         ref[np.abs(s) < 0.1] = 0
         self.ref_dof_pos = (ref + Q0).astype(f32)
 
     # ---------------------------------------------------------------- rewards (t1:576-935)
     def _compute_reward(self):
-        """legged_robot.py:654-680: scale*dt, alphabetical order, clip >= 0."""
+        """legged_robot.py:654-680: scale*dt, alphabetical order, clip >= 0 (only_positive_rewards)."""
         self.rew_terms = {}
         rew = np.zeros(self.N, f32)
-        for name in REWARD_NAMES:
+        for name in self.reward_names:
             r = (getattr(self, "_r_" + name)().astype(f32) * f32(self.reward_scales[name])).astype(f32)
             self.rew_terms[name] = r
             rew = (rew + r).astype(f32)
             self.episode_sums[name] = (self.episode_sums[name] + r).astype(f32)
-        self.rew_buf = np.maximum(rew, 0).astype(f32)
+        self.rew_buf = np.maximum(rew, 0).astype(f32) if self.cfg["rewards.only_positive_rewards"] else rew
 
     def _contact(self):
         return self.contact[:, FEET, 2] > 5.0
@@ -503,10 +627,10 @@ class T1Oracle:
         return (np.exp(-np.abs(a) * f32(100)) + np.exp(-np.abs(b) * f32(100))) / f32(2)
 
     def _r_feet_distance(self):
-        return self._dist_reward(FEET, 0.15, 0.45)
+        return self._dist_reward(FEET, self.cfg["rewards.foot_min_dist"], self.cfg["rewards.foot_max_dist"])
 
     def _r_knee_distance(self):
-        return self._dist_reward(KNEES, 0.12, 0.35)
+        return self._dist_reward(KNEES, self.cfg["rewards.knee_min_dist"], self.cfg["rewards.knee_max_dist"])
 
     def _r_foot_slip(self):
         c = self._contact()
@@ -520,7 +644,7 @@ class T1Oracle:
         cf = c | (sm > 0) | self.last_contacts
         self.last_contacts = c
         first = (self.feet_air_time > 0) & cf
-        self.feet_air_time = (self.feet_air_time + f32(DT)).astype(f32)
+        self.feet_air_time = (self.feet_air_time + f32(self.dt)).astype(f32)
         air = np.clip(self.feet_air_time, 0, 0.5) * first
         self.feet_air_time = (self.feet_air_time * (~cf)).astype(f32)
         return np.sum(air, 1)
@@ -537,7 +661,7 @@ class T1Oracle:
         return (qm + o) / f32(2)
 
     def _r_feet_contact_forces(self):
-        return np.sum(np.clip(_norm(self.contact[:, FEET, :], -1) - f32(500), 0, 400), 1)
+        return np.sum(np.clip(_norm(self.contact[:, FEET, :], -1) - f32(self.cfg["rewards.max_contact_force"]), 0, 400), 1)
 
     def _r_default_joint_pos(self):
         jd = self.dof[:, :, 0] - Q0
@@ -549,7 +673,7 @@ class T1Oracle:
         sm = self._get_gait_phase()
         mh = np.sum(self.rigid[:, FEET, 2] * sm, 1) / np.sum(sm, 1)
         bh = self.root[:, 2] - (mh - f32(0.05))
-        return np.exp(-np.abs(bh - f32(0.965)) * f32(100))
+        return np.exp(-np.abs(bh - f32(self.cfg["rewards.base_height_target"])) * f32(100))
 
     def _r_base_acc(self):
         return np.exp(-_norm(self.last_root_vel - self.root[:, 7:13], 1) * f32(3))
@@ -567,14 +691,16 @@ class T1Oracle:
     def _r_tracking_lin_vel(self):
         st = self._stand()
         d = self.commands[:, :2] - self.base_lin_vel[:, :2]
-        rs = np.exp(-np.sum(d * d, 1) * f32(5))
-        ra = np.exp(-np.sum(np.abs(d), 1) * f32(5 * 2))
+        sigma = f32(self.cfg["rewards.tracking_sigma"])
+        rs = np.exp(-np.sum(d * d, 1) * sigma)
+        ra = np.exp(-np.sum(np.abs(d), 1) * sigma * f32(2))
         return np.where(st, ra, rs)
 
     def _r_tracking_ang_vel(self):
         st = self._stand()
         d = self.commands[:, 2] - self.base_ang_vel[:, 2]
-        return np.where(st, np.exp(-np.abs(d) * f32(10)), np.exp(-(d * d) * f32(5)))
+        sigma = f32(self.cfg["rewards.tracking_sigma"])
+        return np.where(st, np.exp(-np.abs(d) * sigma * f32(2)), np.exp(-(d * d) * sigma))
 
     def _r_feet_clearance(self):
         c = self._contact()
@@ -582,7 +708,8 @@ class T1Oracle:
         self.feet_height = (self.feet_height + (fz - self.last_feet_z)).astype(f32)
         self.last_feet_z = fz.copy()
         sw = f32(1) - self._get_gait_phase()
-        rp = (self.feet_height > 0.02) & (self.feet_height < 0.08)
+        rp = (self.feet_height > f32(self.cfg["rewards.target_feet_height"])) & \
+            (self.feet_height < f32(self.cfg["rewards.target_feet_height_max"]))
         r = np.sum(rp * sw, 1)
         self.feet_height = (self.feet_height * (~c)).astype(f32)
         return r
@@ -608,7 +735,7 @@ class T1Oracle:
         return np.sum(np.square(self.dof[:, :, 1]), 1)
 
     def _r_dof_acc(self):
-        return np.sum(np.square((self.last_dof_vel - self.dof[:, :, 1]) / f32(DT)), 1)
+        return np.sum(np.square((self.last_dof_vel - self.dof[:, :, 1]) / f32(self.dt)), 1)
 
     def _r_collision(self):
         return np.sum((_norm(self.contact[:, [BASE], :], -1) > 0.1).astype(f32), 1)
@@ -645,6 +772,7 @@ class T1Oracle:
                 return self.reset_idx(env_ids)
             finally:
                 self._key_salt = 0
+        MAX_EPISODE_LEN = self.max_episode_length
         curriculum_step = self.common_step_counter % MAX_EPISODE_LEN == 0
         if self.reduce_fn is not None and curriculum_step:
             # sharded: every rank takes part, also with no local resets (the mean is over all ranks' resets)
@@ -674,23 +802,38 @@ class T1Oracle:
             self.root[env_ids, 0] += self._rf(-p3, p3, env_ids, R.SLOT_RESET_ROOT_XY + 0)
             self.root[env_ids, 1] += self._rf(-p3, p3, env_ids, R.SLOT_RESET_ROOT_XY + 1)
         # randomize_dof_props (legged_robot.py:732-783)
-        rf = lambda lo, hi, s: np.stack([self._rf(lo, hi, env_ids, s + j) for j in range(12)], 1)  # noqa: E731
-        self.torque_multi[env_ids] = rf(0.8, 1.2, R.SLOT_DR_TORQUE)
-        self.motor_offsets[env_ids] = rf(-0.035, 0.035, R.SLOT_DR_OFFSET)
-        self.kp_r[env_ids] = rf(0.8, 1.2, R.SLOT_DR_KP) * KP
-        self.kd_r[env_ids] = rf(0.8, 1.2, R.SLOT_DR_KD) * KD
-        self.coulomb[env_ids] = rf(0.1, 1.0, R.SLOT_DR_COULOMB)
-        self.viscous[env_ids] = rf(0.1, 0.9, R.SLOT_DR_VISCOUS)
-        for j in range(12):
-            lo, hi = ARMATURE_RANGE[j]
-            self.armature[env_ids, j] = self._rf(lo, hi, env_ids, R.SLOT_DR_ARMATURE + j)
+        # (a switched-off randomisation keeps the nominal value: unit multiplier, zero offset / friction / armature,
+        # the nominal gains of _compute_torques' else branch, legged_robot.py:1049-1062)
+        rf = lambda rng, s: np.stack([self._rf(rng[0], rng[1], env_ids, s + j) for j in range(12)], 1)  # noqa: E731
+        dr = lambda k: self.cfg["domain_rand." + k]   # noqa: E731
+        if dr("randomize_torque"):
+            self.torque_multi[env_ids] = rf(dr("torque_multiplier_range"), R.SLOT_DR_TORQUE)
+        if dr("randomize_motor_offset"):
+            self.motor_offsets[env_ids] = rf(dr("motor_offset_range"), R.SLOT_DR_OFFSET)
+        if dr("randomize_gains"):
+            self.kp_r[env_ids] = rf(dr("stiffness_multiplier_range"), R.SLOT_DR_KP) * KP
+            self.kd_r[env_ids] = rf(dr("damping_multiplier_range"), R.SLOT_DR_KD) * KD
+        else:
+            self.kp_r[env_ids], self.kd_r[env_ids] = KP, KD
+        if dr("randomize_coulomb_friction"):
+            self.coulomb[env_ids] = rf(dr("joint_coulomb_range"), R.SLOT_DR_COULOMB)
+            self.viscous[env_ids] = rf(dr("joint_viscous_range"), R.SLOT_DR_VISCOUS)
+        if dr("randomize_joint_armature"):
+            if dr("randomize_joint_armature_each_joint"):
+                for j in range(12):
+                    lo, hi = dr(f"joint_{j + 1}_armature_range")
+                    self.armature[env_ids, j] = self._rf(lo, hi, env_ids, R.SLOT_DR_ARMATURE + j)
+            else:   # one draw per env, used for every joint (legged_robot.py:781-783, 936-937)
+                lo, hi = dr("joint_armature_range")
+                self.armature[env_ids] = self._rf(lo, hi, env_ids, R.SLOT_DR_ARMATURE)[:, None]
         # randomize_lag_props (legged_robot.py:604-651)
+        lr = self.lag_ranges
         self.lag_buffer[env_ids] = 0
-        self.lag_timestep[env_ids] = self._ri(0, 31, env_ids, R.SLOT_LAG_ACTION)
+        self.lag_timestep[env_ids] = self._ri(lr["lag"][0], lr["lag"][1] + 1, env_ids, R.SLOT_LAG_ACTION)
         self.dof_lag_buffer[env_ids] = 0
-        self.dof_lag_timestep[env_ids] = self._ri(0, 31, env_ids, R.SLOT_LAG_DOF)
+        self.dof_lag_timestep[env_ids] = self._ri(lr["dof"][0], lr["dof"][1] + 1, env_ids, R.SLOT_LAG_DOF)
         self.imu_lag_buffer[env_ids] = 0
-        self.imu_lag_timestep[env_ids] = self._ri(0, 11, env_ids, R.SLOT_LAG_IMU)
+        self.imu_lag_timestep[env_ids] = self._ri(lr["imu"][0], lr["imu"][1] + 1, env_ids, R.SLOT_LAG_IMU)
         # buffers
         for b in (self.last_last_actions, self.actions, self.last_actions, self.last_dof_vel, self.last_root_vel,
                   self.feet_air_time):
@@ -702,8 +845,8 @@ class T1Oracle:
         self._generate_gait_time(env_ids)
         self._resample_commands()
         ep = {}
-        for k in REWARD_NAMES:
-            ep["rew_" + k] = f32(np.mean(self.episode_sums[k][env_ids]) / EPISODE_S)
+        for k in self.reward_names:
+            ep["rew_" + k] = f32(np.mean(self.episode_sums[k][env_ids]) / self.episode_s)
             self.episode_sums[k][env_ids] = 0
         if self.mesh_type == "trimesh":
             ep["terrain_level"] = f32(np.mean(self.terrain_levels.astype(f32)))
@@ -723,10 +866,11 @@ class T1Oracle:
 
     def _generate_gait_time(self, env_ids):
         """t1_dh_stand_env.py:109-124"""
-        r = np.stack([self._rf(GAIT_RANGE[g][0], GAIT_RANGE[g][1], env_ids, R.SLOT_GAIT_TIME + i)
-                      for i, g in enumerate(GAIT)], 1).astype(f32)
+        rng = [self.cfg["commands.gait_time_range." + g] for g in self.gait]
+        r = np.stack([self._rf(rng[i][0], rng[i][1], env_ids, R.SLOT_GAIT_TIME + i)
+                      for i in range(len(self.gait))], 1).astype(f32)
         s = ((r[:, 0] + r[:, 1]) + r[:, 2]).astype(f32)
-        sc = (r * (f32(MAX_EPISODE_LEN) / s)[:, None]).astype(f32)
+        sc = (r * (f32(self.max_episode_length) / s)[:, None]).astype(f32)
         sc[:, 1:] = sc[:, :-1].copy()
         sc[:, 0] = 0
         self.gait_time[env_ids] = np.cumsum(sc, 1, dtype=f32).astype(np.int32)
@@ -735,7 +879,7 @@ class T1Oracle:
         """legged_robot.py:1138-1158"""
         d = _norm(self.root[env_ids, :2] - self.env_origins[env_ids, :2], 1)
         up = d > self.env_length / 2
-        down = (d < _norm(self.commands[env_ids, :2], 1) * f32(EPISODE_S * 0.5)) & ~up
+        down = (d < _norm(self.commands[env_ids, :2], 1) * f32(self.episode_s * 0.5)) & ~up
         lv = self.terrain_levels[env_ids] + up.astype(np.int64) - down.astype(np.int64)
         rnd = self._ri(0, self.max_terrain_level, env_ids, R.SLOT_TERRAIN_LEVEL_RAND)
         lv = np.where(lv >= self.max_terrain_level, rnd, np.maximum(lv, 0))
@@ -744,6 +888,7 @@ class T1Oracle:
 
     # ---------------------------------------------------------------- observations (t1:368-481)
     def compute_observations(self):
+        os_ = self.obs_scales
         phase = self._get_phase()
         self._compute_ref_state()
         sin_p = np.sin(f32(2 * PI) * phase).astype(f32)
@@ -751,26 +896,35 @@ class T1Oracle:
         stance = self._get_gait_phase()
         cmask = self._contact().astype(f32)
         cmd_in = np.concatenate([sin_p[:, None], cos_p[:, None],
-                                 self.commands[:, :3] * np.array([2, 2, 1], f32)], 1)
+                                 self.commands[:, :3] * np.array([os_["lin_vel"], os_["lin_vel"], os_["ang_vel"]], f32)],
+                                1)
         q, dq = self.dof[:, :, 0], self.dof[:, :, 1]
-        pf = self.ext_forces[:, :2] / f32(EXT_FORCE_MAX[0] + 0.1)
+        pf = self.ext_forces[:, :2] / f32(self.ext_force_max[0] + 0.1)
         pt = self.ext_torques / f32(EXT_TORQUE_MAX + 0.1)
-        priv = np.concatenate([cmd_in, q - Q0, dq * f32(0.05), self.actions, q - self.ref_dof_pos,
-                               self.base_lin_vel * f32(2), self.base_ang_vel * f32(1),
-                               self.base_euler_xyz * f32(1), pf, pt, self.friction[:, None],
+        priv = np.concatenate([cmd_in, (q - Q0) * f32(os_["dof_pos"]), dq * f32(os_["dof_vel"]), self.actions,
+                               q - self.ref_dof_pos,
+                               self.base_lin_vel * f32(os_["lin_vel"]), self.base_ang_vel * f32(os_["ang_vel"]),
+                               self.base_euler_xyz * f32(os_["quat"]), pf, pt, self.friction[:, None],
                                (self.body_mass / f32(30.0))[:, None], stance, cmask], 1).astype(f32)
         if self.measure_heights:                                 # t1_dh_stand_env.py:466-468
             hts = np.clip(self.root[:, 2:3] - f32(0.5) - self.measured_heights, -1, 1) * f32(HEIGHT_OBS_SCALE)
             priv = np.concatenate([priv, hts.astype(f32)], 1)
         ar = np.arange(self.N)
-        lq = self.dof_lag_buffer[ar, :12, self.dof_lag_timestep]
-        ldq = self.dof_lag_buffer[ar, 12:, self.dof_lag_timestep]
-        limu = self.imu_lag_buffer[ar, :, self.imu_lag_timestep]
-        obs = np.concatenate([cmd_in, (lq - Q0) * f32(1), ldq * f32(0.05), self.actions, limu[:, :3] * f32(1),
-                              limu[:, 3:] * f32(1)], 1).astype(f32)
-        u = np.stack([R.uniform(self.seed, self.ids, self.common_step_counter, R.SLOT_OBS_NOISE + j)
-                      for j in range(NUM_SINGLE_OBS)], 1)
-        obs = (obs + (f32(2) * u - f32(1)) * self.noise_vec * f32(NOISE_LEVEL)).astype(f32)
+        if self.add_dof_lag:
+            lq = self.dof_lag_buffer[ar, :12, self.dof_lag_timestep]
+            ldq = self.dof_lag_buffer[ar, 12:, self.dof_lag_timestep]
+        else:   # no lag ring: the joint state itself, after this step's resets (t1_dh_stand_env.py:432-434)
+            lq, ldq = q, dq
+        if self.add_imu_lag:
+            limu = self.imu_lag_buffer[ar, :, self.imu_lag_timestep]
+        else:   # t1_dh_stand_env.py:446-448
+            limu = np.concatenate([self.base_ang_vel, self.base_euler_xyz], 1)
+        obs = np.concatenate([cmd_in, (lq - Q0) * f32(os_["dof_pos"]), ldq * f32(os_["dof_vel"]), self.actions,
+                              limu[:, :3] * f32(os_["ang_vel"]), limu[:, 3:] * f32(os_["quat"])], 1).astype(f32)
+        if self.cfg["noise.add_noise"]:
+            u = np.stack([R.uniform(self.seed, self.ids, self.common_step_counter, R.SLOT_OBS_NOISE + j)
+                          for j in range(NUM_SINGLE_OBS)], 1)
+            obs = (obs + (f32(2) * u - f32(1)) * self.noise_vec * f32(self.cfg["noise.noise_level"])).astype(f32)
         self.obs_hist = np.concatenate([self.obs_hist[:, 1:], obs[:, None]], 1)
         self.priv_hist = np.concatenate([self.priv_hist[:, 1:], priv[:, None]], 1)
         self.obs_buf = self.obs_hist.reshape(self.N, -1).copy()

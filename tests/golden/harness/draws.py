@@ -36,6 +36,12 @@ SITES = {
     ("randomize_dof_props", 752): ("float", R.SLOT_DR_COULOMB, "col"),
     ("randomize_dof_props", 753): ("float", R.SLOT_DR_VISCOUS, "col"),
     ("randomize_dof_props", 780): ("float", R.SLOT_DR_ARMATURE, "i"),
+    # randomize_joint_armature_each_joint = False: one draw per env, used for all 12 joints
+    ("randomize_dof_props", 783): ("float", R.SLOT_DR_ARMATURE, "one"),
+    # the single-component gaits draw the component the omnidirectional walk draws from the same slot
+    ("_resample_walk_sagittal_command", 147): ("float", R.SLOT_CMD_X, "one"),
+    ("_resample_walk_lateral_command", 156): ("float", R.SLOT_CMD_Y, "one"),
+    ("_resample_rotate_command", 168): ("float", R.SLOT_CMD_YAW, "one"),
     ("_create_envs", 1382): ("start_xy", R.SLOT_START_XY, "col"),
     ("_process_rigid_shape_props", 807): ("int", R.SLOT_FRICTION_BUCKET, "one"),
     ("_process_rigid_shape_props", 809): ("bucket", R.SLOT_FRICTION_VALUE, "one"),

@@ -10,7 +10,8 @@ import numpy as np
 import torch
 
 import synth
-from golden_util import assert_close, load, torque_atol, measures_heights, mid_reset, push_interval_s, terrain_curriculum
+from golden_util import (apply_overrides, assert_close, assert_close_nan, cfg_overrides, load, torque_atol,
+                         measures_heights, mid_reset, push_interval_s, terrain_curriculum)
 
 REWARD_NAMES = sorted(["joint_pos", "feet_clearance", "feet_contact_number", "feet_air_time", "foot_slip",
                        "feet_distance", "knee_distance", "feet_rotation", "feet_contact_forces",
@@ -36,6 +37,10 @@ def make_env_for(fx, device="cuda:0"):
         def name_hook(cfg):
             cfg.domain_rand.push_robots = True
             cfg.domain_rand.push_interval_s = push
+    overrides = cfg_overrides(fx)
+    if overrides:   # gen_golden.CONFIG_OVERRIDES: the scenario's settings, applied as the reference's cfg_hook applied them
+        def name_hook(cfg):
+            apply_overrides(cfg, overrides)
     env = make_t1_env(num_envs=int(fx["num_envs"]), mesh_type=str(fx["mesh_type"]), seed=int(fx["seed"]),
                       device=device, cfg_hook=name_hook)
     if heights:
@@ -67,15 +72,16 @@ class Injector:
         n = env.num_envs
         origins = env.env_origins.cpu().numpy()
         roots, dofs = [], []
-        for s in range(10):
+        dec = int(env.cfg.control.decimation)   # one injected state per substep
+        for s in range(dec):
             r, d, rig, con = synth.state(self.seed, n, self.g + s, origins)
             roots.append(r)
             dofs.append(d)
-        self.g += 10
+        self.g += dec
         dev = env.device
         self._keep = [torch.from_numpy(np.stack(roots)).to(dev), torch.from_numpy(np.stack(dofs)).to(dev),
                       torch.from_numpy(rig).to(dev), torch.from_numpy(con).to(dev),
-                      torch.zeros(10, n, 12, device=dev)]
+                      torch.zeros(dec, n, 12, device=dev)]
         inj = _lib.Injected()
         P = _lib.C.cast
         inj.root, inj.dof, inj.rigid, inj.contact, inj.torque_log = [P(t.data_ptr(), _lib.fp) for t in self._keep]
@@ -97,15 +103,20 @@ def snapshot(env):
         feet_height=env.feet_height.cpu().numpy(), episode_length_buf=env.episode_length_buf.cpu().numpy(),
         ext_forces=env.ext_forces.cpu().numpy(), env_origins=env.env_origins.cpu().numpy(),
         root_states=env.root_states.cpu().numpy(), dof_state=env.dof_state.view(n, 12, 2).cpu().numpy(),
-        episode_sums=np.stack([env.episode_sums[k].cpu().numpy() for k in REWARD_NAMES]),
-        extras_episode=np.array([float(ex["rew_" + k]) for k in REWARD_NAMES], np.float32) if ex else None,
+        # a reward term the env leaves out (zero scale) shows as NaN, as in the fixtures
+        episode_sums=np.stack([env.episode_sums[k].cpu().numpy() if k in env.episode_sums
+                               else np.full(n, np.nan, np.float32) for k in REWARD_NAMES]),
+        extras_episode=np.array([float(ex["rew_" + k]) if "rew_" + k in ex else np.nan for k in REWARD_NAMES],
+                                np.float32) if ex else None,
         max_command_x=ex.get("max_command_x") if ex else None,
         terrain_level=float(ex["terrain_level"]) if ex and "terrain_level" in ex else None,
         applied_force=env.applied_force.cpu().numpy(),
         full_obs=env.obs_buf.cpu().numpy(), gait_start=env.gait_start.cpu().numpy(),
         dof_lag=env.dof_lag_timestep.cpu().numpy(), imu_lag=env.imu_lag_timestep.cpu().numpy(),
         lag=env.lag_timestep.cpu().numpy(), kp=env.randomized_p_gains.cpu().numpy(),
-        armature=env.joint_armatures.cpu().numpy(),
+        armature=env.joint_armatures.cpu().numpy(), kd=env.randomized_d_gains.cpu().numpy(),
+        motor_offsets=env.motor_offsets.cpu().numpy(), joint_coulomb=env.randomized_joint_coulomb.cpu().numpy(),
+        joint_viscous=env.randomized_joint_viscous.cpu().numpy(),
         measured_heights=env.measured_heights.cpu().numpy() if env.measure_heights else None)
 
 
@@ -159,10 +170,16 @@ def compare(name, fx, outs):
         assert_close("gait_start", s["gait_start"], fx["step_gait_start"][t], ctx=ctx)
         assert_close("torques", s["torques"], fx["step_torques"][t], atol=torque_atol(), ctx=ctx)
         for k in ("commands", "ref_dof_pos", "feet_air_time", "feet_height", "ext_forces",
-                  "env_origins", "root_states", "episode_sums", "dof_state"):
+                  "env_origins", "root_states", "dof_state"):
             assert_close(k, s[k], fx["step_" + k][t], ctx=ctx)
+        assert_close_nan("episode_sums", s["episode_sums"], fx["step_episode_sums"][t], ctx=ctx)
         assert_close("kp", s["kp"], fx["step_randomized_p_gains"][t], ctx=ctx)
         assert_close("armature", s["armature"], fx["step_joint_armatures"][t], ctx=ctx)
+        # the other per-env PD terms of randomize_dof_props (the torque multiplier, redrawn every substep, shows in torques)
+        assert_close("kd", s["kd"], fx["step_randomized_d_gains"][t], ctx=ctx)
+        assert_close("motor_offsets", s["motor_offsets"], fx["step_motor_offsets"][t], ctx=ctx)
+        assert_close("joint_coulomb", s["joint_coulomb"], fx["step_randomized_joint_coulomb"][t], ctx=ctx)
+        assert_close("joint_viscous", s["joint_viscous"], fx["step_randomized_joint_viscous"][t], ctx=ctx)
         assert_close("obs", s["obs"], fx["step_obs"][t], ctx=ctx)
         assert_close("priv", s["priv"], fx["step_priv"][t], ctx=ctx)
         assert_close("rew", s["rew"], fx["step_rew"][t], ctx=ctx)
@@ -170,7 +187,7 @@ def compare(name, fx, outs):
             np.testing.assert_array_equal(s["measured_heights"], fx["step_measured_heights"][t],
                                           err_msg="measured_heights" + ctx)
         if t > 0:
-            assert_close("extras_episode", s["extras_episode"], fx["step_extras_episode"][t], ctx=ctx)
+            assert_close_nan("extras_episode", s["extras_episode"], fx["step_extras_episode"][t], ctx=ctx)
             assert abs(s["max_command_x"] - float(fx["step_extras_max_command_x"][t])) < 1e-6, ctx
             if str(fx["mesh_type"]) == "trimesh":   # reported whatever the curriculum setting (t1:535-536)
                 assert abs(s["terrain_level"] - float(fx["step_extras_terrain_level"][t])) < 1e-5, ctx

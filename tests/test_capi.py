@@ -63,6 +63,8 @@ int main(void) {
   printf("%zu %zu %zu %zu %zu %zu\n", offsetof(t1env_config, reset_xy_range), offsetof(t1env_buffers, ep_accum),
          offsetof(t1env_model, base_init_state), offsetof(t1env_buffers, contact_vimp), offsetof(t1env_model, self_capsule),
          offsetof(t1env_model, bounce_threshold));
+  printf("%zu %zu %zu\n", offsetof(t1env_config, armature_shared), offsetof(t1env_config, dof_lag_off),
+         offsetof(t1env_config, imu_lag_off));
   return 0;
 }
 '''
@@ -78,7 +80,8 @@ int main(void) {
     assert sizes[5] == _lib.Config.reset_xy_range.offset
     assert sizes[6] == _lib.Buffers.ep_accum.offset
     assert sizes[7] == _lib.Model.base_init_state.offset
-    assert sizes[8:] == [_lib.Buffers.contact_vimp.offset, _lib.Model.self_capsule.offset, _lib.Model.bounce_threshold.offset]
+    assert sizes[8:11] == [_lib.Buffers.contact_vimp.offset, _lib.Model.self_capsule.offset, _lib.Model.bounce_threshold.offset]
+    assert sizes[11:] == [_lib.Config.armature_shared.offset, _lib.Config.dof_lag_off.offset, _lib.Config.imu_lag_off.offset]
 
 
 def test_env_refuses_cpu_device():

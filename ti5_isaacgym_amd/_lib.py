@@ -44,7 +44,8 @@ class Config(C.Structure):
         ("lag_range", i32 * 2), ("dof_lag_range", i32 * 2), ("imu_lag_range", i32 * 2),
         ("torque_mult_range", f32 * 2), ("motor_offset_range", f32 * 2), ("kp_mult_range", f32 * 2),
         ("kd_mult_range", f32 * 2), ("coulomb_range", f32 * 2), ("viscous_range", f32 * 2),
-        ("armature_range", (f32 * 2) * ND), ("reset_dof_range", f32), ("terrain_curriculum", i32),
+        ("armature_range", (f32 * 2) * ND), ("armature_shared", i32), ("dof_lag_off", i32), ("imu_lag_off", i32),
+        ("reset_dof_range", f32), ("terrain_curriculum", i32),
         ("platform", f32), ("env_length", f32), ("num_terrain_rows", i32), ("num_terrain_cols", i32),
         ("lin_vel_obs_scale", f32), ("ang_vel_obs_scale", f32), ("dof_pos_obs_scale", f32),
         ("dof_vel_obs_scale", f32), ("quat_obs_scale", f32),

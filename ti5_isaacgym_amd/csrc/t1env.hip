@@ -98,7 +98,10 @@ __global__ __launch_bounds__(BLOCK) void k_physics_injected(const DynModel* __re
     slot[j] = a * C.action_scale;
   }
   const int lag = B.lag_timestep[n];
-  const int s_dof = 9 - B.dof_lag_timestep[n] % 10, s_imu = 9 - B.imu_lag_timestep[n] % 10;
+  // the substep whose state the observation reads: the last one at lag 0, whatever the decimation (a lag > 0 needs
+  // decimation == 10, t1env_create)
+  const int s_dof = (C.decimation - 1) - B.dof_lag_timestep[n] % 10;
+  const int s_imu = (C.decimation - 1) - B.imu_lag_timestep[n] % 10;
   float* dof_dst = B.dof_hist + ((size_t)n * 4 + (ctr & 3u)) * 24;
   float* imu_dst = B.imu_hist + ((size_t)n * 2 + (ctr & 1u)) * 8;
   const int N = C.num_envs;
@@ -512,6 +515,9 @@ int t1env_create(const t1env_model* model, const t1env_config* cfg, const t1env_
     e->dyn.d5_shift = 0;
     if (const char* ds = getenv("T1ENV_D5_SHIFT"))  // A/B: 1 = the shift as a concurrent launch (k_shift5)
       if (atoi(ds) == 0 || atoi(ds) == 1) e->dyn.d5_shift = atoi(ds);
+    // k_dyn5's in-workgroup shift moves 1 / decimation of the histories per substep through an LDS ring sized for ten
+    // slices (t1env_dyn5.hip SH_ROUNDS); with fewer substeps a slice overruns the ring, so the shift runs as k_shift5
+    if (cfg->decimation < 10) e->dyn.d5_shift = 1;
     e->dyn.d4_shift = 1;
     if (const char* ds = getenv("T1ENV_D4_SHIFT"))  // A/B: 0 = k_dyn4's stand-alone shift ahead of it, in stream order
       if (atoi(ds) == 0 || atoi(ds) == 1) e->dyn.d4_shift = atoi(ds);

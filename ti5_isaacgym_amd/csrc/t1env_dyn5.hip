@@ -592,8 +592,8 @@ __global__ __launch_bounds__(D5_BLOCK) void k_dyn5(const DynModel* __restrict__ 
   const RngKey K = rng_key(C.seed, (uint32_t)(C.env_offset + n), ctr);
   const V3<float> ef = v3<float>(B.applied_force[n * 3 + 0], B.applied_force[n * 3 + 1], B.applied_force[n * 3 + 2]);
   float vi_ft = B.contact_vimp[(size_t)n * NVIMP + vimp_foot(leg)];
-  const int s_dof = 9 - B.dof_lag_timestep[n] % 10;
-  const int s_imu = 9 - B.imu_lag_timestep[n] % 10;
+  const int s_dof = (nsub - 1) - B.dof_lag_timestep[n] % 10;
+  const int s_imu = (nsub - 1) - B.imu_lag_timestep[n] % 10;
   {  // actions = clip(actions) into the step's history slot, the PD constants and action ring staged
     PdStage<64>& P = lds.pd;
     float a[NLEG];

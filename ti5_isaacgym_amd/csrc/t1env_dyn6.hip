@@ -838,8 +838,8 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
       // ---- W2 / W6: shank terrain, W3 / W7: foot terrain (one half of the body's points each); W6 also records the
       // sensor-lag samples and the substep log from the state it reads at S1
       const bool shank = role == 2 || role == 6;
-      const int s_dof = 9 - B.dof_lag_timestep[n] % 10;
-      const int s_imu = 9 - B.imu_lag_timestep[n] % 10;
+      const int s_dof = (nsub - 1) - B.dof_lag_timestep[n] % 10;
+      const int s_imu = (nsub - 1) - B.imu_lag_timestep[n] % 10;
 
       const int slot = (shank ? WC_SHA : WC_FTA) + half;
       const int b = shank ? bsh : bft;
@@ -919,8 +919,8 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
       }
       T1_PROF_MARK(10);
       if (role == 6) {  // the last substep's state (published before R1): its log row, then the lag samples' stores
-        const int s_dof = 9 - B.dof_lag_timestep[n] % 10;
-        const int s_imu = 9 - B.imu_lag_timestep[n] % 10;
+        const int s_dof = (nsub - 1) - B.dof_lag_timestep[n] % 10;
+        const int s_imu = (nsub - 1) - B.imu_lag_timestep[n] % 10;
         BaseState<float> sb;
         float q[NLEG], qd[NLEG];
         read_state_rows(lds.st, lane, sb, q, qd);

@@ -159,8 +159,9 @@ __device__ __forceinline__ LegSetup leg_setup(const DynModel& M, const t1env_con
   }
   LegSetup L;
   L.lag = B.lag_timestep[n];
-  L.s_dof = 9 - B.dof_lag_timestep[n] % 10;
-  L.s_imu = 9 - B.imu_lag_timestep[n] % 10;
+  // (the last substep at lag 0 whatever the decimation; a lag > 0 needs decimation == 10, t1env_create)
+  L.s_dof = (C.decimation - 1) - B.dof_lag_timestep[n] % 10;
+  L.s_imu = (C.decimation - 1) - B.imu_lag_timestep[n] % 10;
   L.dof_dst = B.dof_hist + ((size_t)n * 4 + (ctr & 3u)) * 24;
   L.imu_dst = B.imu_hist + ((size_t)n * 2 + (ctr & 1u)) * 8;
   load_base_params(M, B, n, PB);
@@ -452,7 +453,7 @@ __device__ __forceinline__ void fused_epilogue_obs(const DynModel& M, const t1en
   O.el = el;
   O.pl = is_stand(C, O.cmd) ? 0 : pl;  // post_a's _get_phase zeroing (the state wave stores it)
   if (do_reset) {
-    reset_obs_inputs(M, C, K, O, /*dof=*/PRIV);
+    reset_obs_inputs(M, C, K, O, /*dof=*/PRIV || C.dof_lag_off != 0);
     resample_commands_r(C, A, O.el, O.gt, O.cmd, genv, ctr);
     if constexpr (!PRIV) {
 #pragma unroll
@@ -471,6 +472,7 @@ __device__ __forceinline__ void fused_epilogue_obs(const DynModel& M, const t1en
   } else {
     float li[6];
     imu_sample(lraw, li);
+    if (do_reset) unlagged_reset_samples(C, O, ld, li);
     store_actor_frame(M, C, B, A, n, K, O, ld, li, P);
   }
 }

@@ -384,7 +384,10 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
       r[5] = s5;
       r[6] = s6;
     }
-    {  // 7 feet_air_time (mutates feet_air_time, last_contacts)
+    // (a term with a zero scale has no reward function in the reference, legged_robot.py:351-384, so the state its
+    // function keeps is not advanced either: feet_air_time / last_contacts here, feet_height / last_feet_z below)
+    r[7] = 0.0f;
+    if (C.reward_scales[7] != 0.0f) {  // 7 feet_air_time (mutates feet_air_time, last_contacts)
       float sm0 = ph.stance[0], sm1 = ph.stance[1];
       if (norm3(cmd[0], cmd[1], cmd[2]) < 0.05f) { sm0 = 1.0f; sm1 = 1.0f; }
       const bool filt0 = contact0 || sm0 > 0.0f || lc[0];
@@ -398,7 +401,8 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
       at[1] = a1 * (filt1 ? 0.0f : 1.0f);
       r[7] = air0 + air1;
     }
-    {  // 8 feet_clearance (mutates feet_height, last_feet_z)
+    r[8] = 0.0f;
+    if (C.reward_scales[8] != 0.0f) {  // 8 feet_clearance (mutates feet_height, last_feet_z)
       const float z0 = f0[2], z1 = f1[2];
       const float h0 = fh[0] + (z0 - lfz[0]), h1 = fh[1] + (z1 - lfz[1]);
       lfz[0] = z0; lfz[1] = z1;
@@ -697,8 +701,9 @@ __device__ __forceinline__ void reset_env(const DynModel& M, const t1env_config&
     B.kd[n * 12 + j] = rand_float(C.kd_mult_range[0], C.kd_mult_range[1], K, SLOT_DR_KD + j) * M.d_gains[j];
     B.coulomb[n * 12 + j] = rand_float(C.coulomb_range[0], C.coulomb_range[1], K, SLOT_DR_COULOMB + j);
     B.viscous[n * 12 + j] = rand_float(C.viscous_range[0], C.viscous_range[1], K, SLOT_DR_VISCOUS + j);
-    B.armature[n * 12 + j] =
-        rand_float(C.armature_range[j][0], C.armature_range[j][1], K, SLOT_DR_ARMATURE + j);
+    // (armature_shared: every joint takes joint 0's draw -- one armature per env, legged_robot.py:781-783, 936-937)
+    B.armature[n * 12 + j] = rand_float(C.armature_range[j][0], C.armature_range[j][1], K,
+                                        SLOT_DR_ARMATURE + (C.armature_shared ? 0 : j));
   }
   // randomize_lag_props: zero the lag rings, redraw lag lengths
 #pragma unroll
@@ -931,6 +936,20 @@ __device__ __forceinline__ void load_lagged(const t1env_buffers& B, const t1env_
   ldrow(lraw, lip);
 }
 
+// A sensor without a lag ring (dof_lag_off / imu_lag_off) reads the state itself, so for an env reset this step its
+// new state X (t1_dh_stand_env.py:432-434, 446-448) where a ring reads the zeros its reset left
+__device__ __forceinline__ void unlagged_reset_samples(const t1env_config& C, const ObsIn& X, float (&ld)[24],
+                                                       float (&li)[6]) {
+  if (C.dof_lag_off) {
+#pragma unroll
+    for (int j = 0; j < 12; ++j) { ld[j] = X.dof[2 * j]; ld[12 + j] = X.dof[2 * j + 1]; }
+  }
+  if (C.imu_lag_off) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { li[i] = X.bq.ang[i]; li[3 + i] = X.bq.euler[i]; }
+  }
+}
+
 // X: the inputs as they stand after post_a (reloaded here after a reset)
 __device__ __forceinline__ void post_b_core(const DynModel& M, const t1env_config& C, const t1env_buffers& B,
                                             const t1env_step_args& A, int n, bool do_reset, bool any_reset, ObsIn& X,
@@ -953,6 +972,7 @@ __device__ __forceinline__ void post_b_core(const DynModel& M, const t1env_confi
   T1_PROF_MARK(20);
   if (any_reset && resample_commands_r(C, A, X.el, X.gt, X.cmd, genv, ctr)) strow(B.commands + n * 4, X.cmd);
   imu_sample(lraw, li);
+  if (do_reset) unlagged_reset_samples(C, X, ld, li);
   // ---- compute_observations
   const bool stand = is_stand(C, X.cmd);
   if (stand) {  // _get_phase zeroes the phase counter of standing envs

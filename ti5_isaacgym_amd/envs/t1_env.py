@@ -113,8 +113,54 @@ def set_self_collision(m, tab, enabled=True, bounce_threshold=0.5):
 
 
 def check_supported(cfg):
-    """Configuration switches the HIP path does not implement raise here, before any device work."""
-    dr = cfg.domain_rand
+    """Configuration switches the HIP path does not implement raise here, before any device work: a knob the kernels
+    do not read must not change the task silently (DESIGN.md §5 lists every knob and where it is pinned)."""
+    dr, cm = cfg.domain_rand, cfg.commands
+    if cm.heading_command:
+        # the reference turns commands[:, 3] into a yaw command from the heading error every step
+        # (legged_robot.py:951-954, t1_dh_stand_env.py:141-188)
+        raise NotImplementedError("commands.heading_command = True: the heading controller is not on the HIP path")
+    if not getattr(cm, "sw_switch", True):
+        # the phase then runs on the episode step and does not hold for standing envs (t1_dh_stand_env.py:82-90)
+        raise NotImplementedError("commands.sw_switch = False: the HIP phase is the stand-aware one (sw_switch = True)")
+    if cm.num_commands != 4:
+        raise NotImplementedError(f"commands.num_commands = {cm.num_commands}: the HIP command buffer has 4 columns")
+    if cfg.control.control_type != "P":
+        raise NotImplementedError(f"control.control_type = {cfg.control.control_type!r}: only the position PD "
+                                  "controller 'P' has a HIP kernel")
+    gait = list(getattr(cm, "gait", ()))
+    if len(gait) != 3:
+        raise NotImplementedError("commands.gait: the HIP command scheduler supports exactly 3 gait slots")
+    for g in gait:
+        if g not in GAIT_KINDS:
+            raise NotImplementedError(f"commands.gait entry {g!r}: known gaits are {sorted(GAIT_KINDS)}")
+    for knob in ("randomize_joint_friction", "randomize_joint_damping", "randomize_link_com",
+                 "randomize_base_inertia", "randomize_link_inertia"):
+        # the reference scales the simulator's joint friction / damping, link COMs and inertias with these
+        # (legged_robot.py:711-729, 754-773, 869-883, 921-930); the HIP dynamics has no such term
+        if getattr(dr, knob, False):
+            raise NotImplementedError(f"domain_rand.{knob} = True is not implemented by the HIP dynamics")
+    for knob in ("add_dof_pos_vel_lag", "randomize_lag_timesteps_perstep", "randomize_dof_lag_timesteps_perstep",
+                 "randomize_imu_lag_timesteps_perstep"):
+        if getattr(dr, knob, False):
+            raise NotImplementedError(f"domain_rand.{knob} = True: per-step lag redraws / the split pos-vel lag are "
+                                      "not on the t1_dh_stand path")
+    for flag, rng, cap in (("add_lag", "lag_timesteps_range", 30), ("add_dof_lag", "dof_lag_timesteps_range", 30),
+                           ("add_imu_lag", "imu_lag_timesteps_range", 10)):
+        if not getattr(dr, flag):
+            continue
+        lo, hi = getattr(dr, rng)
+        if not 0 <= lo <= hi <= cap:
+            raise NotImplementedError(f"domain_rand.{rng} = [{lo}, {hi}]: the HIP lag rings hold [0, {cap}] substeps")
+        if hi > 0 and cfg.control.decimation != 10:
+            raise NotImplementedError(f"control.decimation = {cfg.control.decimation} with domain_rand.{flag}: the "
+                                      "HIP lag rings assume 10 substeps per step (switch the lags off)")
+    if not dr.add_ext_force and dr.push_robots:
+        # without add_ext_force the critic frame carries the push velocities instead (t1_dh_stand_env.py:384-388)
+        raise NotImplementedError("domain_rand.add_ext_force = False with push_robots = True: the critic frame's push "
+                                  "terms are not on the HIP path")
+    if cfg.env.use_ref_actions:
+        raise NotImplementedError("env.use_ref_actions = True is not on the t1_dh_stand path")
     if dr.add_ext_force and dr.ext_torque_max != 0:
         # the reference applies the drawn torques to the base too (apply_torques, t1_dh_stand_env.py:243-247); the
         # HIP dynamics applies the base force only (ext_torque_max = 0 in DHT1StandCfg, t1_dh_stand_config.py:201)
@@ -342,18 +388,12 @@ class T1DHStandEnv(VecEnv):
         for k in ("base_height_target", "foot_min_dist", "foot_max_dist", "knee_min_dist", "knee_max_dist",
                   "target_feet_height", "target_feet_height_max", "tracking_sigma", "max_contact_force"):
             setattr(c, k, getattr(r, k))
-        gait = cfg.commands.gait
-        if len(gait) != 3:
-            raise NotImplementedError("the HIP command scheduler supports exactly 3 gait slots")
-        for i, g in enumerate(gait):
+        for i, g in enumerate(cfg.commands.gait):   # (3 known gaits: check_supported)
             c.gait_kind[i] = GAIT_KINDS[g]
             c.gait_time_range[i][0], c.gait_time_range[i][1] = cfg.commands.gait_time_range[g]
         c.ext_force_max[0], c.ext_force_max[1], c.ext_force_max[2] = dr.ext_force_max_x, dr.ext_force_max_y, dr.ext_force_max_z
         c.ext_torque_max = dr.ext_torque_max
         c.push_vel_xy, c.push_ang = dr.max_push_vel_xy, dr.max_push_ang_vel
-        if getattr(dr, "add_dof_pos_vel_lag", False) or dr.randomize_lag_timesteps_perstep or \
-                dr.randomize_dof_lag_timesteps_perstep or dr.randomize_imu_lag_timesteps_perstep:
-            raise NotImplementedError("per-step lag redraws / split pos-vel lag are not on the t1_dh_stand path")
 
         def lag(flag, rnd, rng):
             if not flag:
@@ -362,6 +402,7 @@ class T1DHStandEnv(VecEnv):
         c.lag_range[0], c.lag_range[1] = lag(dr.add_lag, dr.randomize_lag_timesteps, dr.lag_timesteps_range)
         c.dof_lag_range[0], c.dof_lag_range[1] = lag(dr.add_dof_lag, dr.randomize_dof_lag_timesteps, dr.dof_lag_timesteps_range)
         c.imu_lag_range[0], c.imu_lag_range[1] = lag(dr.add_imu_lag, dr.randomize_imu_lag_timesteps, dr.imu_lag_timesteps_range)
+        c.dof_lag_off, c.imu_lag_off = int(not dr.add_dof_lag), int(not dr.add_imu_lag)
 
         def rng(flag, r_, one):
             return tuple(r_) if flag else (one, one)
@@ -378,6 +419,8 @@ class T1DHStandEnv(VecEnv):
             else:
                 rr = (0.0, 0.0)
             c.armature_range[j][0], c.armature_range[j][1] = rr
+        # one draw per env for all joints (legged_robot.py:781-783, 936-937)
+        c.armature_shared = int(bool(dr.randomize_joint_armature) and not dr.randomize_joint_armature_each_joint)
         c.reset_dof_range = 0.1
         c.terrain_curriculum = int(bool(cfg.terrain.curriculum) and self.custom_origins)
         c.platform = float(getattr(cfg.terrain, "platform", 3.0))
