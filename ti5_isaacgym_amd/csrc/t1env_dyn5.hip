@@ -68,6 +68,11 @@ struct Dyn5Lds {  // without the in-workgroup shift's staging (the concurrent sh
   float rsf[2][3][64];   // the report: self-contact forces on the shank / foot (W3)
   float vib[64];         // end-of-step episode of the base-box half (W1 -> W3's report)
 };
+T1_ROWS_ALIGNED(Dyn5Lds, st);
+T1_ROWS_ALIGNED(Dyn5Lds, w1);
+T1_ROWS_ALIGNED(Dyn5Lds, w2);
+T1_ROWS_ALIGNED(Dyn5Lds, w3);
+static_assert(alignof(Dyn5Lds) % 16 == 0, "the rows' offsets are alignments only in an aligned struct");
 struct Dyn5LdsSh : Dyn5Lds {
   ShiftRing ring;        // the in-workgroup history shift's LDS-DMA staging (W1-W3)
 };

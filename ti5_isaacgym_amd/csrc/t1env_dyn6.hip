@@ -148,6 +148,12 @@ struct Dyn6Lds {
   float rtf[2][3][64];    // the report: terrain forces on the shank [0] (W2) / foot [1] (W3)
   float rsf[2][3][64];    // the report: self-contact forces on the shank / foot (W5)
 };
+T1_ROWS_ALIGNED(Dyn6Lds, st);
+T1_ROWS_ALIGNED(Dyn6Lds, wb);
+T1_ROWS_ALIGNED(Dyn6Lds, sj);
+T1_ROWS_ALIGNED(Dyn6Lds, w1);
+T1_ROWS_ALIGNED(Dyn6Lds, wc);
+static_assert(sizeof(Rows4<XCH>) % 16 == 0 && alignof(Dyn6Lds) % 16 == 0, "every wc[i], and the struct itself");
 
 // ---- the history shift through VGPRs.  Output element e of a row-major history (rows of ROW = F * H) is input element
 // e + F unless e is in the row's newest frame (column >= ROW - F), which the epilogue (or k_post_b) of the same
@@ -438,6 +444,9 @@ __device__ __forceinline__ void contact_half(const DynModel& M, const Terrain& T
 // the joint subspaces (W0's own CRBA rows) per joint, the foot's terms ((points 0-3 + 4-7) + self) for joints 5 and 4,
 // then the shank's, added to them in place for joints 3-0 (Cs = C0 + C1, the same sums), the bias G last.  Every
 // element gets leg_apply_terms' operations in its order (the L, Bl and rhs updates of different joints are independent).
+// The contact terms and the subspaces are read as float4 (get4), the bias rows 16 bytes wide (get4w): with the terms or
+// the subspaces read wide the compiler pairs the products of this block's sums differently when it forms its fmas
+// (fma(a, b, c * d) for fma(c, d, a * b)), and the step's results change in the last bits.
 template <int K0, int K1>
 __device__ __forceinline__ void leg_apply_terms_rows(const Rows4<XCH> (&W)[WC_N], const Rows4<R_N>& W1,
                                                      const float rg[NLEG], const SubspaceRows& SR, int lane,
@@ -501,7 +510,7 @@ __device__ __forceinline__ void leg_apply_terms_rows(const Rows4<XCH> (&W)[WC_N]
   joint(kconst<0>{});
   sym_add(Ac_up, C);
   float w1v[R_N];
-  get4(W1, lane, w1v);
+  get4w(W1, lane, w1v);
 #pragma unroll
   for (int i = 0; i < 6; ++i) gc_up[i] += w1v[R_G + i] + c[i];
 }
@@ -1018,7 +1027,11 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
     {
       BaseState<float> sb;
       float q[NLEG], qd[NLEG];
-      read_state_rows(lds.st, lane, sb, q, qd);
+      {
+        float v[Q_N];
+        get4w(lds.st, lane, v);
+        state_unpack(v, sb, q, qd);
+      }
       const M3<float> R0 = quat_to_mat(sb.quat[0], sb.quat[1], sb.quat[2], sb.quat[3]);  // base_frame's F.R0
       LegFK<float> fk;
       leg_fk_chain(M, R0, q, leg, fk);
@@ -1027,8 +1040,8 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
       leg_backward_crba(M, PL, q, qd, leg, dt, fk, Sj, lb, Ab);
 #pragma unroll
       for (int k = 0; k < NLEG; ++k) {  // the joint subspaces to LDS for the fold-in (registers at its peak)
-        lds.sj.r[k][0][lane] = make_float4(Sj[k][0], Sj[k][1], Sj[k][2], Sj[k][3]);
-        lds.sj.r[k][1][lane] = make_float4(Sj[k][4], Sj[k][5], 0.0f, 0.0f);
+        row_put(lds.sj.r[k][0][lane], row_f4{Sj[k][0], Sj[k][1], Sj[k][2], Sj[k][3]});
+        row_put(lds.sj.r[k][1][lane], row_f4{Sj[k][4], Sj[k][5], 0.0f, 0.0f});
       }
     }
     T1_PROF_MARK(2);
@@ -1047,8 +1060,8 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
     float g6[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     {
       float rg[NLEG];  // dt tau_k (W4's torques, the first two rows of wb) + the bias part (W1)
-      const float4 t0 = lds.wb.r[0][lane], t1 = lds.wb.r[1][lane];
-      const float4 g0 = lds.w1.r[0][lane], g1 = lds.w1.r[1][lane];
+      const row_f4 t0 = row_get(lds.wb.r[0][lane]), t1 = row_get(lds.wb.r[1][lane]);
+      const row_f4 g0 = row_get(lds.w1.r[0][lane]), g1 = row_get(lds.w1.r[1][lane]);
       const float tv[NLEG] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y}, gv[NLEG] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y};
       static_assert(WB_TAU == 0 && R_RG == 0, "the torques and the bias rhs lead their rows");
 #pragma unroll
@@ -1066,7 +1079,7 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
     float r[6];
     {
       float v[WB_N];
-      get4(lds.wb, lane, v);
+      get4w(lds.wb, lane, v);
 #pragma unroll
       for (int i = 0; i < 21; ++i) Ac.a[i] = v[WB_AC + i];
 #pragma unroll
@@ -1089,12 +1102,12 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
     backsub_leg(lb, r, dq);
     BaseState<float> sb;
     float q[NLEG], qd[NLEG];
-    read_state_rows(lds.st, lane, sb, q, qd);
+    read_state_rows(lds.st, lane, sb, q, qd);  // as float4: read wide, the integration's fmas pair differently
     integrate_base(sb, r, dt);
     integrate_leg(M, leg, q, qd, dq, dt);
     float v[Q_N];
     state_pack(sb, q, qd, v);
-    put4(lds.st, lane, v);  // the roles read the previous state before S2; after the last substep: the report's
+    put4w(lds.st, lane, v);  // the roles read the previous state before S2; after the last substep: the report's
     T1_PROF_MARK(7);
   }
   T1_CLOCK_LOOP_END();

@@ -4,12 +4,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
+
 #include "t1_dynamics.h"
 #include "t1env_fused.h"  // XCH, K_SHANK / K_FOOT
 
 namespace t1 {
 
-// float4 rows [row][lane]: one ds_write_b128 / ds_read_b128 per 4 values of a lane, conflict-free
+// float4 rows [row][lane]: 4 values of a lane in one 16-byte slot, conflict-free
 template <int K> struct Rows4 { float4 r[(K + 3) / 4][64]; };
 template <int K>
 __device__ __forceinline__ void put4(Rows4<K>& D, int lane, const float (&v)[K]) {
@@ -23,6 +25,33 @@ __device__ __forceinline__ void get4(const Rows4<K>& D, int lane, float (&v)[K])
 #pragma unroll
   for (int r = 0; r < (K + 3) / 4; ++r) {
     const float4 x = D.r[r][lane];
+    v[4 * r] = x.x;
+    if (4 * r + 1 < K) v[4 * r + 1] = x.y;
+    if (4 * r + 2 < K) v[4 * r + 2] = x.z;
+    if (4 * r + 3 < K) v[4 * r + 3] = x.w;
+  }
+}
+// The same rows read and written 16 bytes wide.  At -O1 a float4 copy is taken apart into its four members before the
+// LDS access is selected and comes out as ds_read2_b32 / ds_write2_b32 pairs with an address addition each; a load or
+// store of the compiler's native vector stays one ds_read_b128 / ds_write_b128.  A struct of rows that sits in LDS keeps
+// every member 16-byte aligned (T1_ROWS_ALIGNED): an unaligned b128 access is replayed.
+typedef float row_f4 __attribute__((ext_vector_type(4)));
+static_assert(sizeof(row_f4) == sizeof(float4) && alignof(float4) == 16, "a row slot is one 16-byte LDS access");
+#define T1_ROWS_ALIGNED(S, m) static_assert(offsetof(S, m) % 16 == 0, #S "::" #m ": rows are read and written 16 bytes wide")
+__device__ __forceinline__ row_f4 row_get(const float4& slot) { return *reinterpret_cast<const row_f4*>(&slot); }
+__device__ __forceinline__ void row_put(float4& slot, row_f4 x) { *reinterpret_cast<row_f4*>(&slot) = x; }
+template <int K>
+__device__ __forceinline__ void put4w(Rows4<K>& D, int lane, const float (&v)[K]) {
+#pragma unroll
+  for (int r = 0; r < (K + 3) / 4; ++r)
+    row_put(D.r[r][lane], row_f4{v[4 * r], 4 * r + 1 < K ? v[4 * r + 1] : 0.0f, 4 * r + 2 < K ? v[4 * r + 2] : 0.0f,
+                                 4 * r + 3 < K ? v[4 * r + 3] : 0.0f});
+}
+template <int K>
+__device__ __forceinline__ void get4w(const Rows4<K>& D, int lane, float (&v)[K]) {
+#pragma unroll
+  for (int r = 0; r < (K + 3) / 4; ++r) {
+    const row_f4 x = row_get(D.r[r][lane]);
     v[4 * r] = x.x;
     if (4 * r + 1 < K) v[4 * r + 1] = x.y;
     if (4 * r + 2 < K) v[4 * r + 2] = x.z;

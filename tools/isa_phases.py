@@ -3,7 +3,13 @@ every T1_PROF_MARK into an assembly comment).  Counts follow the code layout: a 
 next mark in the listing, so it is exact for straight-line phases and indicative where branches interleave.
 
     python tools/isa_phases.py [--unit dyn5|dyn6|PATH.hip] [--opt -O1] [--kernel-index 0] [--mem]
-                                [--skeleton MARK] [--listing PATH.s] [extra hipcc flags]
+                                [--skeleton MARK] [--listing PATH.s] [--barriers [--near 6]] [extra hipcc flags]
+
+--barriers reads the product's code instead: the listing of a build WITHOUT the marks (their operands cost registers:
+the marked k_dyn6 spills 35 VGPRs where the product spills none), cut at its `s_barrier`s and loop edges.  Per region it
+prints the instruction mix, the LDS opcode histogram, and for every `s_waitcnt lgkmcnt(N)` with an LDS read pending the
+number of VALU instructions issued since the last LDS read (`valu:N`; --near: what counts as directly behind the read).
+A wait a few VALU instructions behind its read exposes the whole LDS latency on a wave that runs alone on its SIMD.
 
 --mem prints, per region, the memory round trips the wave waits out instead of the instruction mix: its global loads
 and stores, the `s_waitcnt vmcnt` waits that have a global load pending (each one is a memory latency the wave sits
@@ -25,14 +31,15 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(REPO, "ti5_isaacgym_amd", "csrc")
 
 
-def listing(unit, opt, extra, keep=None):
-    """the unit's device assembly; keep: a path to read it from if it exists, and to write it to if not"""
+def listing(unit, opt, extra, keep=None, marks=True):
+    """the unit's device assembly; keep: a path to read it from if it exists, and to write it to if not; marks: the
+    -DT1_ASM_MARKS build (False: the product's code, which the marks' operands and comments do not perturb)"""
     if keep and os.path.exists(keep):
         return open(keep).read().split("\n")
     src = unit if unit.endswith(".hip") else os.path.join(CSRC, f"t1env_{unit}.hip")
     out = keep or os.path.join(tempfile.gettempdir(), f"isa_phases_{os.getpid()}.s")
     subprocess.run(["/opt/rocm/bin/hipcc", opt, "--offload-arch=gfx950", "-std=c++17", "-fno-slp-vectorize",
-                    "--cuda-device-only", "-S", "-DT1_ASM_MARKS", "-I", os.path.join(REPO, "include"), "-I", CSRC,
+                    "--cuda-device-only", "-S", *(["-DT1_ASM_MARKS"] if marks else []), "-I", os.path.join(REPO, "include"), "-I", CSRC,
                     *extra, "-o", out, src], check=True)
     return open(out).read().split("\n")
 
@@ -120,12 +127,134 @@ def print_skeleton(lines, mark):
             run += 1
 
 
+def barrier_regions(lines):
+    """The unmarked listing cut at its `s_barrier`s and at the edges of its outermost loops: [(loop header or None,
+    segment index within that stretch, first listing line, [instruction text])].  The compiler's block comments
+    (`in Loop: Header=BB0_60 Depth=1`, `Parent Loop BB0_60 Depth=1`, `=>This Loop Header: Depth=1`) say which loop a
+    block belongs to; a block without one is outside every loop."""
+    out, loop, seg, body, first = [], None, 0, [], 0
+
+    def close(k):
+        nonlocal body, first
+        if body:
+            out.append((loop, seg, first, body))
+        body, first = [], k
+
+    for k, l in enumerate(lines):
+        t = l.strip()
+        is_block = re.match(r"^(\.LBB\d+_\d+:|; %bb\.\d+:)", t)
+        if is_block:
+            new = loop
+            m = re.search(r"in Loop: Header=(BB\d+_\d+) Depth=(\d+)", t)
+            if re.search(r"=>This (Inner )?Loop Header: Depth=1\b", t):
+                new = t.split(":")[0].lstrip(".L")
+            elif m and m.group(2) == "1":
+                new = m.group(1)
+            elif m or "Loop Header: Depth=" in t:
+                pass  # an inner block: its `Parent Loop ... Depth=1` comment follows; the outer loop stays
+            else:
+                new = None
+            if new != loop:
+                close(k)
+                loop, seg = new, 0
+            continue
+        m = re.search(r"Parent Loop (BB\d+_\d+) Depth=1\b", t)
+        if m and m.group(1) != loop:
+            close(k)
+            loop, seg = m.group(1), 0
+        if not t or t.startswith(";") or t.startswith(".") or t.endswith(":"):
+            continue
+        if t.split()[0] == "s_barrier":
+            close(k)
+            seg += 1
+            continue
+        if not body:
+            first = k
+        body.append(t)
+    close(len(lines))
+    return out
+
+
+def lgkm_waits(body):
+    """[(VALU instructions since the last LDS read, the wait's lgkmcnt)] of the `s_waitcnt lgkmcnt(N)` that have an LDS
+    read pending (issued since the last lgkmcnt(0))"""
+    out, since, pending = [], 0, False
+    for t in body:
+        op = t.split()[0]
+        if op.startswith("ds_read") or op.startswith("ds_bpermute") or op.startswith("ds_swizzle"):
+            since, pending = 0, True
+        elif op.startswith("v_") and not op.startswith("v_accvgpr"):
+            since += 1
+        elif op == "s_waitcnt":
+            m = re.search(r"lgkmcnt\((\d+)\)", t)
+            if m and pending:
+                out.append((since, int(m.group(1))))
+                pending = int(m.group(1)) != 0
+    return out
+
+
+def print_barrier_regions(lines, near):
+    """Per region between barriers: the instruction mix, the LDS opcode histogram and, per lgkmcnt wait, the VALU
+    instructions since the last LDS read (`valu:lgkmcnt`).  A loop's last segment and its first (from the header to the
+    first barrier) are one region at run time: the wrap-around is printed as such.  In k_dyn6 the roles' substep loops
+    follow each other in the listing (W4, W1, W5, the terrain halves, W0): the core wave's is the last loop with two
+    barriers, its S1 -> S2 region segment 1 and its S2 -> S1 region the wrap-around."""
+    regs = barrier_regions(lines)
+    loops = collections.OrderedDict()
+    for loop, seg, first, body in regs:
+        loops.setdefault((loop, first if loop is None else None), []).append((seg, first, body))
+    two = [k for k, v in loops.items() if k[0] is not None and max(s for s, _, _ in v) >= 2]
+    for key, segs in loops.items():
+        loop = key[0]
+        merged = {}
+        for seg, first, body in segs:  # a segment split by an inner loop's blocks: one region
+            merged.setdefault(seg, [first, []])[1].extend(body)
+        nseg = max(merged) if merged else 0
+        rows = []
+        if loop is not None and nseg >= 1:
+            for seg in range(1, nseg):
+                if seg in merged:
+                    rows.append((f"barrier {seg} -> {seg + 1}", merged[seg][0], merged[seg][1]))
+            wrap = merged.get(nseg, [0, []])[1] + merged.get(0, [0, []])[1]
+            rows.append((f"barrier {nseg} -> 1 (wraps)", merged.get(nseg, merged[min(merged)])[0], wrap))
+        else:
+            for seg in sorted(merged):
+                rows.append((f"segment {seg}", merged[seg][0], merged[seg][1]))
+        tag = f"loop {loop}" + ("  [the last two-barrier loop: the core wave's]" if two and key == two[-1] else "") \
+            if loop else "outside loops"
+        for name, first, body in rows:
+            if len(body) < 8:
+                continue
+            c = mix(body)
+            print(f"{tag}, {name}, listing line {first + 1}: total {len(body)}  " +
+                  "  ".join(f"{k} {c[k]}" for k in ("valu", "salu", "lds", "smem", "vmem", "wait")))
+            h = collections.Counter(t.split()[0] for t in body if t.startswith("ds_"))
+            if h:
+                print("    lds: " + "  ".join(f"{k} {v}" for k, v in sorted(h.items())))
+            fp = collections.Counter()
+            for t in body:  # the arithmetic a data-movement change must leave as it was: f32 opcodes, encoding suffix off
+                op = re.sub(r"_(e32|e64|dpp|sdwa)$", "", t.split()[0])
+                if op.startswith("v_permlane") or re.match(r"v_(pk_)?\w*f32$", op) and not op.startswith("v_cvt"):
+                    fp["v_fma_f32+v_fmac_f32" if op in ("v_fma_f32", "v_fmac_f32") else op] += 1
+            if fp:
+                print("    f32: " + "  ".join(f"{k} {v}" for k, v in sorted(fp.items())))
+            w = lgkm_waits(body)
+            if w:
+                close = sum(1 for v, _ in w if v <= near)
+                print(f"    lgkmcnt waits with a read pending: {len(w)}, within {near} VALU of the last read: {close}")
+                print("    valu:lgkmcnt  " + " ".join(f"{v}:{n}" for v, n in w))
+
+
 def main():
     args = sys.argv[1:]
-    ki, unit, opt, want_mem, skeleton, keep = 0, "dyn5", "-O1", False, None, None
-    while args and args[0] in ("--kernel-index", "--unit", "--opt", "--mem", "--skeleton", "--listing"):
+    ki, unit, opt, want_mem, skeleton, keep, barriers, near = 0, "dyn5", "-O1", False, None, None, False, 6
+    while args and args[0] in ("--kernel-index", "--unit", "--opt", "--mem", "--skeleton", "--listing", "--barriers",
+                               "--near"):
         if args[0] == "--mem":
             want_mem, args = True, args[1:]
+            continue
+        if args[0] == "--barriers":
+            barriers, args = True, args[1:]
             continue
         key, val, args = args[0], args[1], args[2:]
         if key == "--kernel-index":
@@ -136,10 +265,15 @@ def main():
             skeleton = val
         elif key == "--listing":
             keep = val
+        elif key == "--near":
+            near = int(val)
         else:
             opt = val
-    name, lines = kernel_lines(listing(unit, opt, args, keep), ki)
+    name, lines = kernel_lines(listing(unit, opt, args, keep, marks=not barriers), ki)
     print(name[:60], opt)
+    if barriers:
+        print_barrier_regions(lines, near)
+        return
     if skeleton:
         print_skeleton(lines, skeleton)
         return
