@@ -104,6 +104,53 @@ template <typename R> T1_HD R dot(V3<R> a, V3<R> b) { return a.x * b.x + a.y * b
 template <typename R> T1_HD V3<R> cross(V3<R> a, V3<R> b) {
   return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
 }
+// Sums and products with the contraction written in the source.  Left to itself the compiler fuses a
+// product into a neighbouring sum where its combiner finds one, and which product of a two-product sum it takes moves
+// with the code around the sum.  With PIN, in device code and for float, fmad / fnmad are one fma and pmul / sum2 / dif2
+// round the named product on its own whatever consumes it; a function that opens with T1_NO_CONTRACT leaves nothing of
+// its own text to the combiner either.  Without PIN, in host code and for double they are the plain expressions,
+// contracted as the compiler likes: what every build compiled before there was a PIN.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define T1_NO_CONTRACT _Pragma("clang fp contract(off)")
+template <bool PIN, typename R> inline constexpr bool fp_pinned = false;
+template <> inline constexpr bool fp_pinned<true, float> = true;
+#else
+#define T1_NO_CONTRACT
+template <bool PIN, typename R> inline constexpr bool fp_pinned = false;
+#endif
+template <bool PIN = true, typename R> T1_HD R fmad(R a, R b, R c) {  // a b + c
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (fp_pinned<PIN, R>) return __builtin_fmaf(a, b, c);
+#endif
+  return a * b + c;
+}
+template <bool PIN = true, typename R> T1_HD R fnmad(R a, R b, R c) {  // c - a b
+#if defined(__HIP_DEVICE_COMPILE__)
+  if constexpr (fp_pinned<PIN, R>) return __builtin_fmaf(-a, b, c);
+#endif
+  return c - a * b;
+}
+template <bool PIN = true, typename R> T1_HD R pmul(R a, R b) {  // a b, rounded on its own
+  if constexpr (fp_pinned<PIN, R>) {
+    T1_NO_CONTRACT
+    return a * b;
+  } else {
+    return a * b;
+  }
+}
+// a b + c d and a b - c d: product P (0: a b, 1: c d) is rounded on its own, the other one rides in the fma
+template <int P, bool PIN = true, typename R> T1_HD R sum2(R a, R b, R c, R d) {
+  static_assert(P == 0 || P == 1, "the product rounded on its own");
+  if constexpr (fp_pinned<PIN, R>) return P == 1 ? fmad(a, b, pmul(c, d)) : fmad(c, d, pmul(a, b));
+  else return a * b + c * d;
+}
+template <int P, bool PIN = true, typename R> T1_HD R dif2(R a, R b, R c, R d) {
+  static_assert(P == 0 || P == 1, "the product rounded on its own");
+  if constexpr (fp_pinned<PIN, R>) return P == 1 ? fmad(a, b, -pmul(c, d)) : fnmad(c, d, pmul(a, b));
+  else return a * b - c * d;
+}
+// a value kept as its two factors, for a consumer that takes the product into an fma of its own
+template <typename R> struct Prod { R a, b; };
 // fast reciprocal / square root: hardware v_rcp_f32 / v_sqrt_f32 (1 ulp) on the device, exact on the host
 T1_HD float rcp(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)

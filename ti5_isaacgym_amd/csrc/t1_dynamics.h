@@ -139,13 +139,26 @@ template <typename R> T1_HD void sym_rank1(Sym6<R>& S, R c, const R w[6]) {
     for (int j = i; j < 6; ++j) S.a[sidx(i, j)] += ci * w[j];
   }
 }
-template <typename R> T1_HD void sym_mul(const Sym6<R>& S, const R x[6], R y[6]) {
+// PIN: every term an fma onto the running sum, written out (the core wave's fold-in after S2); otherwise the plain sum,
+// its contraction the compiler's
+template <bool PIN = false, typename R> T1_HD void sym_mul(const Sym6<R>& S, const R x[6], R y[6]) {
+  if constexpr (PIN) {
+    T1_NO_CONTRACT
 #pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    R acc = R(0);
+    for (int i = 0; i < 6; ++i) {
+      R acc = R(0);
 #pragma unroll
-    for (int j = 0; j < 6; ++j) acc += sget(S, i, j) * x[j];
-    y[i] = acc;
+      for (int j = 0; j < 6; ++j) acc = fmad(sget(S, i, j), x[j], acc);
+      y[i] = acc;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+      R acc = R(0);
+#pragma unroll
+      for (int j = 0; j < 6; ++j) acc += sget(S, i, j) * x[j];
+      y[i] = acc;
+    }
   }
 }
 // spatial inertia of a body about O in world axes from (m, com c rel O, Ic world) ; [[Io, [h]x],[[h]x^T, m]]
@@ -178,8 +191,20 @@ template <typename R> T1_HD void crf(const R a[6], const R b[6], R out[6]) {
   V3<R> o1 = cross(w, n) + cross(v, f), o2 = cross(w, f);
   out[0] = o1.x; out[1] = o1.y; out[2] = o1.z; out[3] = o2.x; out[4] = o2.y; out[5] = o2.z;
 }
-template <typename R> T1_HD R dot6(const R a[6], const R b[6]) {
-  return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3] + a[4] * b[4] + a[5] * b[5];
+// HEAD < 0: the plain sum, its contraction the compiler's.  HEAD 0 / 1 (the core wave's fold-in after S2): the
+// contraction pinned -- the sum's head a0 b0 + a1 b1 is the one place with two possible fusions, HEAD names the product
+// that stays a plain multiplication; the other one and every later term are fmas in the sum's order.
+template <int HEAD = -1, typename R> T1_HD R dot6(const R a[6], const R b[6]) {
+  static_assert(HEAD <= 1, "the unfused product of the head: a0 b0 or a1 b1");
+  if constexpr (HEAD < 0) {
+    return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3] + a[4] * b[4] + a[5] * b[5];
+  } else {
+    T1_NO_CONTRACT
+    R acc = HEAD == 0 ? fmad(a[1], b[1], a[0] * b[0]) : fmad(a[0], b[0], a[1] * b[1]);
+#pragma unroll
+    for (int i = 2; i < 6; ++i) acc = fmad(a[i], b[i], acc);
+    return acc;
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1188,34 +1213,37 @@ T1_HD void leg_assemble(const DynModel& M, const Terrain& T, const LegParams<R>&
 // [base 0..5, leg 0..5].  On return out.L/Bl hold the unit factor L (off-diagonal), L's diagonal holds
 // 1/D, Abb and rhs_b hold the Schur-complement updates, and out.rhs the forward-substituted leg rhs.
 // The Schur updates do not depend on Abb's value, so a leg can be eliminated into its own contribution.
-template <typename R> T1_HD void eliminate_leg(LegBlock<R>& lb, Sym6<R>& Abb, R rhs_b[6]) {
+// PIN (here and in solve_base, backsub_leg, integrate_base, integrate_leg): the contraction of every sum is written out
+// (t1_common.h: fmad, fnmad, pmul, dif2), in the order the -O1 build of k_dyn6's core wave contracted the plain text;
+// without it the plain text, its contraction the compiler's.
+template <bool PIN = false, typename R> T1_HD void eliminate_leg(LegBlock<R>& lb, Sym6<R>& Abb, R rhs_b[6]) {
 #pragma unroll
   for (int k = NLEG - 1; k >= 0; --k) {
     const R inv = rcp(lb.L[sidx(k, k)]);
     // ancestors of leg dof k: leg dofs i < k, then base dofs 5..0
     R a_leg[NLEG], a_base[6];
 #pragma unroll
-    for (int i = 0; i < k; ++i) a_leg[i] = lb.L[sidx(i, k)] * inv;
+    for (int i = 0; i < k; ++i) a_leg[i] = pmul<PIN>(lb.L[sidx(i, k)], inv);
 #pragma unroll
-    for (int r = 0; r < 6; ++r) a_base[r] = lb.Bl[r][k] * inv;
+    for (int r = 0; r < 6; ++r) a_base[r] = pmul<PIN>(lb.Bl[r][k], inv);
     // H_ij -= a_i * H_kj for ancestor pairs (i, j) -- every pair on the path
 #pragma unroll
     for (int i = 0; i < k; ++i) {
 #pragma unroll
-      for (int jj = 0; jj <= i; ++jj) lb.L[sidx(jj, i)] -= a_leg[i] * lb.L[sidx(jj, k)];
+      for (int jj = 0; jj <= i; ++jj) lb.L[sidx(jj, i)] = fnmad<PIN>(a_leg[i], lb.L[sidx(jj, k)], lb.L[sidx(jj, i)]);
 #pragma unroll
-      for (int r = 0; r < 6; ++r) lb.Bl[r][i] -= a_leg[i] * lb.Bl[r][k];
+      for (int r = 0; r < 6; ++r) lb.Bl[r][i] = fnmad<PIN>(a_leg[i], lb.Bl[r][k], lb.Bl[r][i]);
     }
 #pragma unroll
     for (int r = 0; r < 6; ++r)
 #pragma unroll
-      for (int c = r; c < 6; ++c) Abb.a[sidx(r, c)] -= a_base[r] * lb.Bl[c][k];
+      for (int c = r; c < 6; ++c) Abb.a[sidx(r, c)] = fnmad<PIN>(a_base[r], lb.Bl[c][k], Abb.a[sidx(r, c)]);
     // forward substitution of the rhs (L^-T pass): b_i -= L_ki b_k
     const R bk = lb.rhs[k];
 #pragma unroll
-    for (int i = 0; i < k; ++i) lb.rhs[i] -= a_leg[i] * bk;
+    for (int i = 0; i < k; ++i) lb.rhs[i] = fnmad<PIN>(a_leg[i], bk, lb.rhs[i]);
 #pragma unroll
-    for (int r = 0; r < 6; ++r) rhs_b[r] -= a_base[r] * bk;
+    for (int r = 0; r < 6; ++r) rhs_b[r] = fnmad<PIN>(a_base[r], bk, rhs_b[r]);
     // store the factor
     lb.L[sidx(k, k)] = inv;
 #pragma unroll
@@ -1225,8 +1253,10 @@ template <typename R> T1_HD void eliminate_leg(LegBlock<R>& lb, Sym6<R>& Abb, R 
   }
 }
 
-// dense LDL^T of the 6x6 base block with the same (leaf-first) convention and solve in place.
-template <typename R> T1_HD void solve_base(Sym6<R>& A, R b[6]) {
+// dense LDL^T of the 6x6 base block with the same (leaf-first) convention and solve in place.  PIN: x_k's scaling by
+// 1/D_k rides in its first subtraction, and x_0, a bare product, is also returned as its factors (x0) for the
+// integration's first sum (integrate_base).
+template <bool PIN = false, typename R> T1_HD void solve_base(Sym6<R>& A, R b[6], Prod<R>* x0 = nullptr) {
   R invd[6];
 #pragma unroll
   for (int k = 5; k >= 0; --k) {
@@ -1234,31 +1264,34 @@ template <typename R> T1_HD void solve_base(Sym6<R>& A, R b[6]) {
     invd[k] = inv;
     R a[6];
 #pragma unroll
-    for (int i = 0; i < k; ++i) a[i] = A.a[sidx(i, k)] * inv;
+    for (int i = 0; i < k; ++i) a[i] = pmul<PIN>(A.a[sidx(i, k)], inv);
 #pragma unroll
     for (int i = 0; i < k; ++i)
 #pragma unroll
-      for (int jj = 0; jj <= i; ++jj) A.a[sidx(jj, i)] -= a[i] * A.a[sidx(jj, k)];
+      for (int jj = 0; jj <= i; ++jj) A.a[sidx(jj, i)] = fnmad<PIN>(a[i], A.a[sidx(jj, k)], A.a[sidx(jj, i)]);
 #pragma unroll
-    for (int i = 0; i < k; ++i) { b[i] -= a[i] * b[k]; A.a[sidx(i, k)] = a[i]; }
+    for (int i = 0; i < k; ++i) { b[i] = fnmad<PIN>(a[i], b[k], b[i]); A.a[sidx(i, k)] = a[i]; }
   }
+  if constexpr (PIN) *x0 = Prod<R>{b[0], invd[0]};
 #pragma unroll
-  for (int k = 0; k < 6; ++k) b[k] *= invd[k];
+  for (int k = 0; k < 6; ++k)
+    if (!PIN || k == 0) b[k] = pmul<PIN>(b[k], invd[k]);
 #pragma unroll
   for (int k = 0; k < 6; ++k)
 #pragma unroll
-    for (int i = 0; i < k; ++i) b[k] -= A.a[sidx(i, k)] * b[i];
+    for (int i = 0; i < k; ++i)
+      b[k] = PIN && i == 0 ? dif2<1, PIN>(b[k], invd[k], A.a[sidx(0, k)], b[0]) : fnmad<PIN>(A.a[sidx(i, k)], b[i], b[k]);
 }
 
 // back substitution for a leg once the base solution x_b is known: x_k = rhs_k / D_k - sum_anc L_ki x_i
-template <typename R> T1_HD void backsub_leg(const LegBlock<R>& lb, const R xb[6], R x[NLEG]) {
+template <bool PIN = false, typename R> T1_HD void backsub_leg(const LegBlock<R>& lb, const R xb[6], R x[NLEG]) {
 #pragma unroll
   for (int k = 0; k < NLEG; ++k) {
-    R v = lb.rhs[k] * lb.L[sidx(k, k)];
+    R v = PIN ? dif2<1, PIN>(lb.rhs[k], lb.L[sidx(k, k)], lb.Bl[0][k], xb[0]) : lb.rhs[k] * lb.L[sidx(k, k)];
 #pragma unroll
-    for (int r = 0; r < 6; ++r) v -= lb.Bl[r][k] * xb[r];
+    for (int r = PIN ? 1 : 0; r < 6; ++r) v = fnmad<PIN>(lb.Bl[r][k], xb[r], v);
 #pragma unroll
-    for (int i = 0; i < k; ++i) v -= lb.L[sidx(i, k)] * x[i];
+    for (int i = 0; i < k; ++i) v = fnmad<PIN>(lb.L[sidx(i, k)], x[i], v);
     x[k] = v;
   }
 }
@@ -1611,25 +1644,46 @@ T1_HD void leg_apply_contacts(const Sym6<R>& C0, const R c0[6], const Sym6<R>& C
 
 // Semi-implicit Euler of the base with the solved velocity change (+ the omega x v term that turns the
 // spatial base acceleration into the classical acceleration of the base origin).
-template <typename R> T1_HD void integrate_base(BaseState<R>& s, const R delta[6], R dt) {
-  V3<R> w_new = v3<R>(s.w[0] + delta[0], s.w[1] + delta[1], s.w[2] + delta[2]);
-  V3<R> vO_new = v3<R>(s.vo[0] + delta[3], s.vo[1] + delta[4], s.vo[2] + delta[5]);
-  V3<R> vb_new = vO_new + dt * cross(w_new, vO_new);
-  s.w[0] = w_new.x; s.w[1] = w_new.y; s.w[2] = w_new.z;
-  s.vo[0] = vb_new.x; s.vo[1] = vb_new.y; s.vo[2] = vb_new.z;
-  s.pos[0] += dt * vb_new.x; s.pos[1] += dt * vb_new.y; s.pos[2] += dt * vb_new.z;
-  // quaternion: q += 0.5 dt [w, 0] (x) q  (world-frame angular velocity), renormalised
-  R qx = s.quat[0], qy = s.quat[1], qz = s.quat[2], qw = s.quat[3];
-  R hx = R(0.5) * dt * w_new.x, hy = R(0.5) * dt * w_new.y, hz = R(0.5) * dt * w_new.z;
-  R nx = qx + (hx * qw + hy * qz - hz * qy);
-  R ny = qy + (hy * qw + hz * qx - hx * qz);
-  R nz = qz + (hz * qw + hx * qy - hy * qx);
-  R nw = qw - (hx * qx + hy * qy + hz * qz);
-  R inv = rcp(fsqrt(nx * nx + ny * ny + nz * nz + nw * nw));
-  s.quat[0] = nx * inv; s.quat[1] = ny * inv; s.quat[2] = nz * inv; s.quat[3] = nw * inv;
+template <bool PIN = false, typename R>
+T1_HD void integrate_base(BaseState<R>& s, const R delta[6], R dt, const Prod<R>* d0 = nullptr) {
+  if constexpr (PIN) {  // d0: delta[0] as its factors (solve_base); of two leading products the second is rounded alone,
+    T1_NO_CONTRACT      // except in the quaternion's z line
+    V3<R> w_new = v3<R>(fmad(d0->a, d0->b, s.w[0]), s.w[1] + delta[1], s.w[2] + delta[2]);
+    V3<R> vO_new = v3<R>(s.vo[0] + delta[3], s.vo[1] + delta[4], s.vo[2] + delta[5]);
+    V3<R> vb_new = v3<R>(fmad(dt, dif2<1>(w_new.y, vO_new.z, w_new.z, vO_new.y), vO_new.x),   // vO + dt (w x vO)
+                         fmad(dt, dif2<1>(w_new.z, vO_new.x, w_new.x, vO_new.z), vO_new.y),
+                         fmad(dt, dif2<1>(w_new.x, vO_new.y, w_new.y, vO_new.x), vO_new.z));
+    s.w[0] = w_new.x; s.w[1] = w_new.y; s.w[2] = w_new.z;
+    s.vo[0] = vb_new.x; s.vo[1] = vb_new.y; s.vo[2] = vb_new.z;
+    s.pos[0] = fmad(dt, vb_new.x, s.pos[0]); s.pos[1] = fmad(dt, vb_new.y, s.pos[1]); s.pos[2] = fmad(dt, vb_new.z, s.pos[2]);
+    R qx = s.quat[0], qy = s.quat[1], qz = s.quat[2], qw = s.quat[3];
+    R hx = R(0.5) * dt * w_new.x, hy = R(0.5) * dt * w_new.y, hz = R(0.5) * dt * w_new.z;
+    R nx = qx + fnmad(hz, qy, sum2<1>(hx, qw, hy, qz));
+    R ny = qy + fnmad(hx, qz, sum2<1>(hy, qw, hz, qx));
+    R nz = qz + fnmad(hy, qx, sum2<0>(hz, qw, hx, qy));
+    R nw = qw - fmad(hz, qz, sum2<1>(hx, qx, hy, qy));
+    R inv = rcp(fsqrt(fmad(nw, nw, fmad(nz, nz, sum2<1>(nx, nx, ny, ny)))));
+    s.quat[0] = nx * inv; s.quat[1] = ny * inv; s.quat[2] = nz * inv; s.quat[3] = nw * inv;
+  } else {
+    V3<R> w_new = v3<R>(s.w[0] + delta[0], s.w[1] + delta[1], s.w[2] + delta[2]);
+    V3<R> vO_new = v3<R>(s.vo[0] + delta[3], s.vo[1] + delta[4], s.vo[2] + delta[5]);
+    V3<R> vb_new = vO_new + dt * cross(w_new, vO_new);
+    s.w[0] = w_new.x; s.w[1] = w_new.y; s.w[2] = w_new.z;
+    s.vo[0] = vb_new.x; s.vo[1] = vb_new.y; s.vo[2] = vb_new.z;
+    s.pos[0] += dt * vb_new.x; s.pos[1] += dt * vb_new.y; s.pos[2] += dt * vb_new.z;
+    // quaternion: q += 0.5 dt [w, 0] (x) q  (world-frame angular velocity), renormalised
+    R qx = s.quat[0], qy = s.quat[1], qz = s.quat[2], qw = s.quat[3];
+    R hx = R(0.5) * dt * w_new.x, hy = R(0.5) * dt * w_new.y, hz = R(0.5) * dt * w_new.z;
+    R nx = qx + (hx * qw + hy * qz - hz * qy);
+    R ny = qy + (hy * qw + hz * qx - hx * qz);
+    R nz = qz + (hz * qw + hx * qy - hy * qx);
+    R nw = qw - (hx * qx + hy * qy + hz * qz);
+    R inv = rcp(fsqrt(nx * nx + ny * ny + nz * nz + nw * nw));
+    s.quat[0] = nx * inv; s.quat[1] = ny * inv; s.quat[2] = nz * inv; s.quat[3] = nw * inv;
+  }
 }
 // joint speeds clamped to the URDF velocity limit like PhysX max joint velocity
-template <typename R>
+template <bool PIN = false, typename R>
 T1_HD void integrate_leg(const DynModel& M, int leg, R q[NLEG], R qd[NLEG], const R delta[NLEG], R dt) {
 #pragma unroll
   for (int k = 0; k < NLEG; ++k) {
@@ -1637,7 +1691,8 @@ T1_HD void integrate_leg(const DynModel& M, int leg, R q[NLEG], R qd[NLEG], cons
     R vl = R(M.vel_limit[6 * leg + k]);
     v = v > vl ? vl : (v < -vl ? -vl : v);
     qd[k] = v;
-    q[k] += dt * v;
+    if constexpr (PIN) q[k] = fmad(dt, v, q[k]);
+    else q[k] += dt * v;
   }
 }
 

@@ -444,33 +444,33 @@ __device__ __forceinline__ void contact_half(const DynModel& M, const Terrain& T
 // the joint subspaces (W0's own CRBA rows) per joint, the foot's terms ((points 0-3 + 4-7) + self) for joints 5 and 4,
 // then the shank's, added to them in place for joints 3-0 (Cs = C0 + C1, the same sums), the bias G last.  Every
 // element gets leg_apply_terms' operations in its order (the L, Bl and rhs updates of different joints are independent).
-// The contact terms and the subspaces are read as float4 (get4), the bias rows 16 bytes wide (get4w): with the terms or
-// the subspaces read wide the compiler pairs the products of this block's sums differently when it forms its fmas
-// (fma(a, b, c * d) for fma(c, d, a * b)), and the step's results change in the last bits.
+// Every row is read 16 bytes wide; the contraction of the block's sums is written out (T1_NO_CONTRACT, fmad, dot6's
+// head), so how a row is loaded no longer decides which product the compiler fuses.
 template <int K0, int K1>
 __device__ __forceinline__ void leg_apply_terms_rows(const Rows4<XCH> (&W)[WC_N], const Rows4<R_N>& W1,
                                                      const float rg[NLEG], const SubspaceRows& SR, int lane,
                                                      LegBlock<float>& out, Sym6<float>& Ac_up, float gc_up[6]) {
+  T1_NO_CONTRACT
   static_assert(K0 == K_SHANK && K1 == K_FOOT && K1 == NLEG - 1, "the foot's terms first, then the shank's");
   auto terms = [&](int i, Sym6<float>& Cb, float cb[6]) {  // contact body i (0 shank, 1 foot): (half 0 + half 1) + self
     float va[XCH];
-    get4(W[2 * i], lane, va);
+    get4w(W[2 * i], lane, va);
     {
       float vb[XCH];
-      get4(W[2 * i + 1], lane, vb);
+      get4w(W[2 * i + 1], lane, vb);
 #pragma unroll
       for (int k = 0; k < XCH; ++k) va[k] = va[k] + vb[k];
     }
     {
       float vs[XCH];
-      get4(W[WC_SSH + i], lane, vs);
+      get4w(W[WC_SSH + i], lane, vs);
 #pragma unroll
       for (int k = 0; k < XCH; ++k) va[k] = va[k] + vs[k];
     }
     sym_unpack(va, Cb, cb);
   };
   auto subspace = [&](int k, float (&Sk)[6]) {
-    const float4 x = SR.r[k][0][lane], y = SR.r[k][1][lane];
+    const row_f4 x = row_get(SR.r[k][0][lane]), y = row_get(SR.r[k][1][lane]);
     Sk[0] = x.x; Sk[1] = x.y; Sk[2] = x.z; Sk[3] = x.w; Sk[4] = y.x; Sk[5] = y.y;
   };
   Sym6<float> C;  // C1 (the foot), then Cs = C0 + C1
@@ -478,17 +478,20 @@ __device__ __forceinline__ void leg_apply_terms_rows(const Rows4<XCH> (&W)[WC_N]
   terms(1, C, c);
   auto joint = [&](auto jc) {
     constexpr int jj = decltype(jc)::value;
+    // dot6's head as the -O1 build contracted the plain sums: with the foot's terms alone (joints 5 and 4) the second
+    // product is rounded on its own, but for joint 5's diagonal; with the shank's terms added the first one is
+    constexpr int DH = jj >= 4 ? 1 : 0, DH_DIAG = jj == 4 ? 1 : 0;
     float Sj[6], u[6];
     subspace(jj, Sj);
-    sym_mul(C, Sj, u);
-    const float sc = dot6(Sj, c);
-    out.L[sidx(jj, jj)] += dot6(Sj, u);
+    sym_mul<true>(C, Sj, u);
+    const float sc = dot6<DH>(Sj, c);
+    out.L[sidx(jj, jj)] += dot6<DH_DIAG>(Sj, u);
     out.rhs[jj] += rg[jj] - sc;
 #pragma unroll
     for (int k = 0; k < jj; ++k) {
       float Sk[6];
       subspace(k, Sk);
-      out.L[sidx(k, jj)] += dot6(Sk, u);
+      out.L[sidx(k, jj)] += dot6<DH>(Sk, u);
     }
 #pragma unroll
     for (int r = 0; r < 6; ++r) out.Bl[r][jj] += u[r];
@@ -1065,14 +1068,14 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
       const float tv[NLEG] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y}, gv[NLEG] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y};
       static_assert(WB_TAU == 0 && R_RG == 0, "the torques and the bias rhs lead their rows");
 #pragma unroll
-      for (int k = 0; k < NLEG; ++k) rg[k] = dt * tv[k] + gv[k];
+      for (int k = 0; k < NLEG; ++k) rg[k] = pmul(dt, tv[k]) + gv[k];  // two roundings, as the -O1 build of the plain text
       leg_apply_terms_rows<K_SHANK, K_FOOT>(lds.wc, lds.w1, rg, lds.sj, lane, lb, Ab, g6);
     }
     T1_PROF_MARK(5);
     float rb[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) rb[i] = -g6[i];
-    eliminate_leg(lb, Ab, rb);
+    eliminate_leg<true>(lb, Ab, rb);
     T1_PROF_MARK(6);
     // the base system: (base block + both base-box halves, W4) + the left leg + the right leg, in every lane
     Sym6<float> Ac;
@@ -1097,14 +1100,15 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
       halves(rb[i], l, rr);
       r[i] = (r[i] + l) + rr;
     }
-    solve_base(Ac, r);
+    Prod<float> r0;  // r[0] as its factors: the integration takes the product into its own fma
+    solve_base<true>(Ac, r, &r0);
     float dq[NLEG];
-    backsub_leg(lb, r, dq);
+    backsub_leg<true>(lb, r, dq);
     BaseState<float> sb;
     float q[NLEG], qd[NLEG];
-    read_state_rows(lds.st, lane, sb, q, qd);  // as float4: read wide, the integration's fmas pair differently
-    integrate_base(sb, r, dt);
-    integrate_leg(M, leg, q, qd, dq, dt);
+    read_state_rows<true>(lds.st, lane, sb, q, qd);
+    integrate_base<true>(sb, r, dt, &r0);
+    integrate_leg<true>(M, leg, q, qd, dq, dt);
     float v[Q_N];
     state_pack(sb, q, qd, v);
     put4w(lds.st, lane, v);  // the roles read the previous state before S2; after the last substep: the report's
@@ -1113,14 +1117,18 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
   T1_CLOCK_LOOP_END();
   BaseState<float> sb;
   float q[NLEG], qd[NLEG];
-  read_state_rows(lds.st, lane, sb, q, qd);
+  read_state_rows<true>(lds.st, lane, sb, q, qd);
+  // the output addresses (episodes, joint and root state) are formed again from the env index: the prologue's, held
+  // across the substep loop for these stores, are spilled
+  int no = n;
+  asm volatile("" : "+v"(no));
   if (active) {
-    B.contact_vimp[(size_t)n * NVIMP + vimp_foot(leg)] = vi_ft;
-    B.contact_vimp[(size_t)n * NVIMP + vimp_shank(leg)] = vi_sh;
+    B.contact_vimp[(size_t)no * NVIMP + vimp_foot(leg)] = vi_ft;
+    B.contact_vimp[(size_t)no * NVIMP + vimp_shank(leg)] = vi_sh;
 #pragma unroll
     for (int k = 0; k < NLEG; ++k) {
-      B.dof_state[n * 24 + 2 * (j0 + k)] = q[k];
-      B.dof_state[n * 24 + 2 * (j0 + k) + 1] = qd[k];
+      B.dof_state[no * 24 + 2 * (j0 + k)] = q[k];
+      B.dof_state[no * 24 + 2 * (j0 + k) + 1] = qd[k];
     }
   }
   float (*FR)[NE6] = FUSED ? lds.fr : nullptr;
@@ -1137,7 +1145,7 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
   {
     BaseFrame<float> F;
     base_frame(sb, F);
-    leg_report_rigid<NE6>(M, B, PB, sb, F, q, qd, n, leg, active, e, FR);
+    leg_report_rigid<NE6>(M, B, PB, sb, F, q, qd, no, leg, active, e, FR);
   }
   T1_PROF_MARK(10);
   __syncthreads();  // RB: the contact-force report's parts in LDS

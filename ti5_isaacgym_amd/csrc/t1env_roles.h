@@ -88,10 +88,14 @@ __device__ __forceinline__ void state_unpack(const float (&v)[Q_N], BaseState<fl
 #pragma unroll
   for (int k = 0; k < NLEG; ++k) { q[k] = v[Q_Q + k]; qd[k] = v[Q_QD + k]; }
 }
+// WIDE: for a reader whose sums are contracted in its source (the core wave); how a row is loaded moves the compiler's
+// own contraction of the sums that use it
+template <bool WIDE = false>
 __device__ __forceinline__ void read_state_rows(const Rows4<Q_N>& st, int lane, BaseState<float>& sb, float q[NLEG],
                                                 float qd[NLEG]) {
   float v[Q_N];
-  get4(st, lane, v);
+  if constexpr (WIDE) get4w(st, lane, v);
+  else get4(st, lane, v);
   state_unpack(v, sb, q, qd);
 }
 __device__ __forceinline__ void sym_pack(const Sym6<float>& A, const float g[6], float (&v)[XCH]) {
