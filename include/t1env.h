@@ -40,7 +40,22 @@ extern "C" {
 #define T1_NPRIV 73       /* single_num_privileged_obs */
 #define T1_HIST 66        /* frame_stack */
 #define T1_CHIST 3        /* c_frame_stack */
-#define T1_NREW 24        /* active reward terms, alphabetical order */
+#define T1_NREW 28        /* reward terms with a kernel, alphabetical order (T1_REW_* below) */
+
+/* Indices of the reward terms in reward_scales / episode_sums / extras (alphabetical, as the reference iterates its
+ * scales, legged_robot.py:351-384; termination is added after the only_positive_rewards clip, :654-680). */
+enum {
+  T1_REW_ACTION_SMOOTHNESS = 0, T1_REW_BASE_ACC, T1_REW_BASE_HEIGHT, T1_REW_COLLISION, T1_REW_DEFAULT_JOINT_POS,
+  T1_REW_DOF_ACC, T1_REW_DOF_VEL, T1_REW_DOF_VEL_LIMITS, T1_REW_FEET_AIR_TIME, T1_REW_FEET_CLEARANCE,
+  T1_REW_FEET_CONTACT_FORCES, T1_REW_FEET_CONTACT_NUMBER, T1_REW_FEET_DISTANCE, T1_REW_FEET_ROTATION,
+  T1_REW_FEET_STUMBLE, T1_REW_FOOT_SLIP, T1_REW_JOINT_POS, T1_REW_KNEE_DISTANCE, T1_REW_LOW_SPEED,
+  T1_REW_ORIENTATION, T1_REW_STAND_STILL, T1_REW_STAND_SYSMETRY, T1_REW_TERMINATION, T1_REW_TORQUES,
+  T1_REW_TRACK_VEL_HARD, T1_REW_TRACKING_ANG_VEL, T1_REW_TRACKING_LIN_VEL, T1_REW_VEL_MISMATCH_EXP
+};
+/* columns of the 32-wide extras rows and of ep_accum behind the reward terms */
+#define T1_EX_TERRAIN_LEVEL T1_NREW  /* extras: terrain level mean */
+#define T1_ACC_COUNT T1_NREW         /* ep_accum: number of envs reset this step */
+#define T1_ACC_LEVEL (T1_NREW + 1)   /* ep_accum: terrain level sum */
 
 #define T1ENV_EXTRAS_RING 64  /* steps an extras["episode"] view stays valid (the runner logs every 24) */
 
@@ -94,6 +109,9 @@ typedef struct t1env_config {
   int32_t only_positive_rewards;
   float base_height_target, foot_min_dist, foot_max_dist, knee_min_dist, knee_max_dist;
   float target_feet_height, target_feet_height_max, tracking_sigma, max_contact_force;
+  /* rewards.soft_dof_vel_limit: read by dof_vel_limits only (t1_dh_stand_env.py:942-946); neither reference config
+   * defines it, so the host layer requires it when that term has a scale */
+  float soft_dof_vel_limit;
   float gait_time_range[3][2];  /* per gait slot (walk_omni, stand, walk_omni) */
   int32_t gait_kind[3];         /* 0 = walk_omnidirectional, 1 = stand, 2 = walk_sagittal, 3 = walk_lateral, 4 = rotate */
   float ext_force_max[3], ext_torque_max;
@@ -160,7 +178,7 @@ typedef struct t1env_buffers {
   float* ext_forces;        /* (N,3) */
   float* ext_torques;       /* (N,3) */
   float* applied_force;     /* (N,3) base force for the next simulate (ENV_SPACE) */
-  float* episode_sums;      /* (24,N) */
+  float* episode_sums;      /* (T1_NREW,N) = (28,N) */
   float* kp;                /* (N,12) randomized_p_gains */
   float* kd;                /* (N,12) randomized_d_gains */
   float* motor_offsets;     /* (N,12) */
@@ -182,11 +200,11 @@ typedef struct t1env_buffers {
   int32_t* terrain_levels;  /* (N,) */
   int32_t* terrain_types;   /* (N,) */
   float* terrain_origins;   /* (rows, cols, 3) */
-  float* extras;            /* (T1ENV_EXTRAS_RING, 32) ring of extras["episode"]: [0,24) rew_<name> means, [24]
+  float* extras;            /* (T1ENV_EXTRAS_RING, 32) ring of extras["episode"]: [0,28) rew_<name> means, [28]
                                terrain level mean.  A step with args.counter = c writes slot (c+1) % RING
                                (t1env_reset_all: c % RING); a step without resets carries the previous slot */
-  float* ep_accum;          /* (32,) per-step reduction scratch: [0,24) sums over reset envs, [24] count,
-                               [25] terrain level sum; zeroed by the library */
+  float* ep_accum;          /* (32,) per-step reduction scratch: [0,28) sums over reset envs, [28] count,
+                               [29] terrain level sum; zeroed by the library */
   float* contact_vimp;      /* (N,6) restitution episodes of the contact bodies (left shank, left foot, right shank,
                                right foot, base-box halves of the left / right leg): the approach speed a body's
                                current terrain contact began with, 0 when it touches nothing; zeroed at reset

@@ -9,7 +9,10 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("T1ENV_LIB") or os.path.join(HERE, "_lib", "libt1env_hip.so")  # override: A/B builds
 
-NB, ND, MAXC, NOBS, NPRIV, HIST, CHIST, NREW = 13, 12, 48, 47, 73, 66, 3, 24
+NB, ND, MAXC, NOBS, NPRIV, HIST, CHIST, NREW = 13, 12, 48, 47, 73, 66, 3, 28
+
+# columns of the 32-wide extras rows / ep_accum behind the NREW reward terms (include/t1env.h T1_EX_* / T1_ACC_*)
+EX_TERRAIN_LEVEL, ACC_COUNT, ACC_LEVEL = NREW, NREW, NREW + 1
 
 f32, i32, u32 = C.c_float, C.c_int32, C.c_uint32
 fp, u8p, i32p, i64p = C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
@@ -38,7 +41,7 @@ class Config(C.Structure):
         ("reward_scales", f32 * NREW), ("only_positive_rewards", i32),
         ("base_height_target", f32), ("foot_min_dist", f32), ("foot_max_dist", f32), ("knee_min_dist", f32),
         ("knee_max_dist", f32), ("target_feet_height", f32), ("target_feet_height_max", f32),
-        ("tracking_sigma", f32), ("max_contact_force", f32),
+        ("tracking_sigma", f32), ("max_contact_force", f32), ("soft_dof_vel_limit", f32),
         ("gait_time_range", (f32 * 2) * 3), ("gait_kind", i32 * 3),
         ("ext_force_max", f32 * 3), ("ext_torque_max", f32), ("push_vel_xy", f32), ("push_ang", f32),
         ("lag_range", i32 * 2), ("dof_lag_range", i32 * 2), ("imu_lag_range", i32 * 2),

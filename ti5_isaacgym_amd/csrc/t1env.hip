@@ -5,7 +5,7 @@
 // t1env_dynamics.hip runs the 10 substeps, the post-physics epilogue and, in extra workgroups on the CUs the
 // dynamics leave idle, the 65/2-frame history shift.  Split sequence (command-curriculum steps, golden parity):
 //   k_dyn4<FUSED=false> (+ shift workgroups) -> k_post_a -> k_post_b
-//   k_post_a   : base kinematics, command/ext-force callback, termination, 24 rewards (alphabetical),
+//   k_post_a   : base kinematics, command/ext-force callback, termination, 28 rewards (alphabetical),
 //                episode sums, per-step extras reduction (legged_robot.py:458-489, 509-517, 654-680)
 //   k_post_b   : masked reset_idx, compute_observations -> newest obs/priv frame, last_* bookkeeping, reset-row
 //                zeroing, extras finalisation (legged_robot.py:490-502, t1_dh_stand_env.py:368-559)
@@ -150,10 +150,10 @@ __global__ __launch_bounds__(BLOCK) void k_post_b(const DynModel* __restrict__ M
   const t1env_config& C = *Cp;
   const bool live = n < C.num_envs;
   const bool do_reset = live && B.reset_buf[n] != 0;
-  const bool any_reset = B.ep_accum[24] > 0.0f;
+  const bool any_reset = B.ep_accum[T1_ACC_COUNT] > 0.0f;
   if (live) post_b_env(*Mp, C, B, A, n, do_reset, any_reset);
   // extras["episode"]["terrain_level"] = mean level over all envs after this step's resets (legged_robot.py:1158)
-  if (C.custom_origins && any_reset) wave_atomic_add(B.ep_accum + 25, live ? (float)B.terrain_levels[n] : 0.0f);
+  if (C.custom_origins && any_reset) wave_atomic_add(B.ep_accum + T1_ACC_LEVEL, live ? (float)B.terrain_levels[n] : 0.0f);
   // reset_idx zeroes the obs / critic history of the reset envs (t1:548-558): k_shift wrote the 65 (2) older
   // frames of every row, so the wave zeroes those of its reset envs here, one row at a time, coalesced
   uint64_t m = __ballot(do_reset);
@@ -232,7 +232,8 @@ void k_shift5(ShiftArgs S, FusedArgs FA, int N) {
 
 // k_shift4c: the same concurrent shift beside k_dyn4 (config 5: 32768 envs, fp16 histories).  A k_dyn4
 // wave holds 433 of a SIMD's 512 registers per lane, so a shift wave must stay within 72 (amdgpu_waves_per_eu(7, 8)) to
-// share the SIMD; its 148 KB of LDS leaves room for the shift's 1 KB of handoff words.
+// share the SIMD; its 150 KB of LDS (153,608 B with the 28 episode-sum rows staged) leaves room for the shift's 1 KB of
+// handoff words in a CU's 160 KB.
 constexpr int T1_D4_SHIFT_UNROLL = 3;
 template <bool FUSED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8)))
@@ -262,8 +263,8 @@ __global__ void k_finalize(t1env_buffers B, const t1env_config* __restrict__ Cp,
 __global__ __launch_bounds__(256) void k_terrain_level_sum(t1env_buffers B, const t1env_config* __restrict__ Cp) {
   const int n = blockIdx.x * blockDim.x + threadIdx.x;
   const t1env_config& C = *Cp;
-  const float v = (n < C.num_envs && C.custom_origins && B.ep_accum[24] > 0.0f) ? (float)B.terrain_levels[n] : 0.0f;
-  wave_atomic_add(B.ep_accum + 25, v);
+  const float v = (n < C.num_envs && C.custom_origins && B.ep_accum[T1_ACC_COUNT] > 0.0f) ? (float)B.terrain_levels[n] : 0.0f;
+  wave_atomic_add(B.ep_accum + T1_ACC_LEVEL, v);
 }
 
 // -----------------------------------------------------------------------------------------------------
@@ -392,7 +393,7 @@ __global__ __launch_bounds__(BLOCK) void k_reset_all(const DynModel* __restrict_
   float contrib[T1_NREW];
   for (int k = 0; k < T1_NREW; ++k) contrib[k] = live ? B.episode_sums[(size_t)k * C.num_envs + n] : 0.0f;
   for (int k = 0; k < T1_NREW; ++k) wave_atomic_add(B.ep_accum + k, contrib[k]);
-  wave_atomic_add(B.ep_accum + 24, live ? 1.0f : 0.0f);
+  wave_atomic_add(B.ep_accum + T1_ACC_COUNT, live ? 1.0f : 0.0f);
   if (!live) return;
   const uint32_t genv = (uint32_t)(C.env_offset + n);
   // t1env_reset_idx (mask), and t1env_reset_all after the first step (env.reset() on a stepped env): the between-step

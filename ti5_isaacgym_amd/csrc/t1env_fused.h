@@ -94,7 +94,7 @@ __device__ __forceinline__ void epilogue_finalize_parts(const t1env_config& C, c
   prev = __shfl(prev, 0, 64);
   if (prev != (unsigned)dyn_blocks - 1u) return;
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-  static_assert(EP_PART_ROW == 32, "8 float4 per row");
+  static_assert(EP_PART_ROW == 32 && T1_ACC_LEVEL < EP_PART_ROW, "8 float4 per row: the rewards, the count, the level sum");
   const float4* P = reinterpret_cast<const float4*>(FA.ep_part);
   const int q = lane & 7;
   float4 s = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -121,8 +121,8 @@ __device__ __forceinline__ void epilogue_finalize_parts(const t1env_config& C, c
   const float c0 = __shfl(s.x, src, 64), c1 = __shfl(s.y, src, 64), c2 = __shfl(s.z, src, 64), c3 = __shfl(s.w, src, 64);
   const int c = lane & 3;
   const float mine = c == 0 ? c0 : c == 1 ? c1 : c == 2 ? c2 : c3;
-  const float cnt = __shfl(mine, 24, 64);    // reset count
-  const float lvl = __shfl(mine, 25, 64);    // terrain-level sum
+  const float cnt = __shfl(mine, T1_ACC_COUNT, 64);  // reset count
+  const float lvl = __shfl(mine, T1_ACC_LEVEL, 64);  // terrain-level sum
   const int slot = (int)((A.counter + 1u) % T1ENV_EXTRAS_RING);
   float* ex = B.extras + (size_t)slot * 32;
   const float* prevx = B.extras + (size_t)((slot + T1ENV_EXTRAS_RING - 1) % T1ENV_EXTRAS_RING) * 32;
@@ -130,7 +130,7 @@ __device__ __forceinline__ void epilogue_finalize_parts(const t1env_config& C, c
     float v = prevx[lane];
     if (cnt > 0.0f) {
       if (lane < T1_NREW) v = (mine / cnt) / C.episode_length_s;
-      else if (lane == 24) v = lvl / (float)C.num_envs;
+      else if (lane == T1_EX_TERRAIN_LEVEL) v = lvl / (float)C.num_envs;
     }
     ex[lane] = v;
   }
@@ -300,7 +300,7 @@ __device__ __forceinline__ void stage_epilogue_inputs(const t1env_buffers& B, in
 // The fused step's post-physics for the NE envs of one workgroup, run by four waves after the epilogue barrier (lane =
 // env; lanes >= NE shadow an env of the workgroup and store nothing), every input from LDS (fresh outputs FR, staged
 // state E, the clipped actions in ACT0 (joints 0-5) / ACT1 (joints 6-11)).  This function is the two post_a waves:
-// both run post_a's callback + termination prefix; PART = POST_A_REWARDS then the 24 rewards, their stores and extras
+// both run post_a's callback + termination prefix; PART = POST_A_REWARDS then the 28 rewards, their stores and extras
 // sums and the reset rows, POST_A_STATE the state stores, reset_idx of the resetting envs (their new state, commands
 // redrawn) and the terrain-level sum.  The observations are the other two waves' (fused_epilogue_obs).  After one
 // barrier the rewards wave signals completion (the extras finaliser).
@@ -381,7 +381,7 @@ __device__ __forceinline__ void fused_epilogue_staged(const DynModel& M, const t
   }
   T1_PROF_MARK(14);
   // the terrain-level sum reads the levels reset_idx may just have changed
-  wave_sum_store(ep_row + 25, (C.custom_origins && active) ? (float)B.terrain_levels[n] : 0.0f);
+  wave_sum_store(ep_row + T1_ACC_LEVEL, (C.custom_origins && active) ? (float)B.terrain_levels[n] : 0.0f);
   __builtin_amdgcn_s_waitcnt(0);
   __syncthreads();  // E2
   T1_PROF_MARK(15);

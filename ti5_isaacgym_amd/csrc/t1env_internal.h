@@ -57,7 +57,7 @@ int t1_launch_dynamics(const t1::DynModel* d_model, const t1env_config* d_cfg, c
                        const t1::ShiftArgs& S, const DynLaunch& cfg, const FusedArgs* fused, hipStream_t s,
                        bool shift_prelaunched = false, const SubLog* log = nullptr);
 // Whether the history shift should run as its own launch ahead of the dynamics: the dynamics workgroups (one
-// per CU for k_dyn4: 148 KB of LDS) leave fewer than MIN_SHIFT_BLOCKS CUs idle, and shift workgroups of the
+// per CU for k_dyn4: 150 KB of LDS) leave fewer than MIN_SHIFT_BLOCKS CUs idle, and shift workgroups of the
 // dynamics launch would each hold a whole CU's LDS for a small slice of the 26 KB/env stream.
 bool t1_shift_prelaunch(int num_envs, const DynLaunch& cfg);
 // k_dyn5 (t1env_dyn5.hip): the same contract as t1_launch_dynamics; each workgroup shifts its own history rows

@@ -159,14 +159,14 @@ __device__ __forceinline__ void wave_sum_store_n(float* row, float (&v)[K]) {
 // Run by one wave after every env's contribution to ep_accum is complete; zeroes ep_accum.
 __device__ __forceinline__ void finalize_extras(const t1env_buffers& B, const t1env_config& C, int slot) {
   const int t = threadIdx.x & 63;
-  const float cnt = atomicAdd(B.ep_accum + 24, 0.0f);  // device-scope read of the other blocks' atomics
+  const float cnt = atomicAdd(B.ep_accum + T1_ACC_COUNT, 0.0f);  // device-scope read of the other blocks' atomics
   float* ex = B.extras + (size_t)slot * 32;
   const float* prev = B.extras + (size_t)((slot + T1ENV_EXTRAS_RING - 1) % T1ENV_EXTRAS_RING) * 32;
   if (t < 32) {
     float v = prev[t];
     if (cnt > 0.0f) {
       if (t < T1_NREW) v = (atomicAdd(B.ep_accum + t, 0.0f) / cnt) / C.episode_length_s;
-      else if (t == 24) v = atomicAdd(B.ep_accum + 25, 0.0f) / (float)C.num_envs;
+      else if (t == T1_EX_TERRAIN_LEVEL) v = atomicAdd(B.ep_accum + T1_ACC_LEVEL, 0.0f) / (float)C.num_envs;
     }
     ex[t] = v;
   }
@@ -341,7 +341,7 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
   const bool contact0 = c0[2] > 5.0f, contact1 = c1[2] > 5.0f;
   float r[T1_NREW];
   if constexpr (PART != POST_A_STATE) {
-    {  // 0 action_smoothness
+    {  // action_smoothness
       float t1s = 0.0f, t2s = 0.0f, t3s = 0.0f;
 #pragma unroll
       for (int j = 0; j < 12; ++j) {
@@ -351,29 +351,29 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
         t2s += d2 * d2;
         t3s += fabsf(a[j] * 1.0f);
       }
-      r[0] = (t1s + t2s) + 0.05f * t3s;
+      r[T1_REW_ACTION_SMOOTHNESS] = (t1s + t2s) + 0.05f * t3s;
     }
-    {  // 1 base_acc (root velocity after a push, like the reference's root_states)
+    {  // base_acc (root velocity after a push, like the reference's root_states)
       float s = 0.0f;
 #pragma unroll
       for (int i = 0; i < 6; ++i) { const float d = lrv[i] - root[7 + i]; s += d * d; }
-      r[1] = expf(-sqrtf(s) * 3.0f);
+      r[T1_REW_BASE_ACC] = expf(-sqrtf(s) * 3.0f);
     }
-    {  // 2 base_height
+    {  // base_height
       const float mh = (f0[2] * ph.stance[0] + f1[2] * ph.stance[1]) / (ph.stance[0] + ph.stance[1]);
       const float bh = root[2] - (mh - 0.05f);
-      r[2] = expf(-fabsf(bh - C.base_height_target) * 100.0f);
+      r[T1_REW_BASE_HEIGHT] = expf(-fabsf(bh - C.base_height_target) * 100.0f);
     }
-    r[3] = norm3(cfb[0], cfb[1], cfb[2]) > 0.1f ? 1.0f : 0.0f;  // 3 collision (penalised_contact_indices = base)
-    {  // 4 default_joint_pos
+    r[T1_REW_COLLISION] = norm3(cfb[0], cfb[1], cfb[2]) > 0.1f ? 1.0f : 0.0f;  // collision (penalised_contact_indices = base)
+    {  // default_joint_pos
       float jd[12], s = 0.0f;
 #pragma unroll
       for (int j = 0; j < 12; ++j) { jd[j] = dof[2 * j] - M.default_dof_pos[j]; s += jd[j] * jd[j]; }
       float yr = norm3(jd[0], jd[1], jd[5]) + norm3(jd[6], jd[7], jd[11]);
       yr = clampf(yr - 0.1f, 0.0f, 50.0f);
-      r[4] = expf(-yr * 100.0f) - 0.01f * sqrtf(s);
+      r[T1_REW_DEFAULT_JOINT_POS] = expf(-yr * 100.0f) - 0.01f * sqrtf(s);
     }
-    {  // 5 dof_acc, 6 dof_vel
+    {  // dof_acc, dof_vel
       float s5 = 0.0f, s6 = 0.0f;
 #pragma unroll
       for (int j = 0; j < 12; ++j) {
@@ -381,13 +381,28 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
         s5 += d * d;
         s6 += dof[2 * j + 1] * dof[2 * j + 1];
       }
-      r[5] = s5;
-      r[6] = s6;
+      r[T1_REW_DOF_ACC] = s5;
+      r[T1_REW_DOF_VEL] = s6;
+    }
+    // The four terms DHT1StandCfg leaves at scale 0 (dof_vel_limits, feet_stumble, stand_sysmetry here; termination
+    // after the clip below): with a zero scale nothing is evaluated (soft_dof_vel_limit is then not set) and the
+    // term's r is +0, so it adds +0.0f to rew and its episode sum stays 0
+    r[T1_REW_DOF_VEL_LIMITS] = 0.0f;
+    if (C.reward_scales[T1_REW_DOF_VEL_LIMITS] != 0.0f) {  // dof_vel_limits (t1:942-946)
+      float s = 0.0f;
+#pragma unroll
+      for (int j = 0; j < 12; ++j) {
+        // the reference overwrites the limits of joints 4 and 9 with 10 in the reward function; here only the reward
+        // sees that (M.vel_limit also bounds the dynamics' joint velocities)
+        const float lim = (j == 4 || j == 9) ? 10.0f : M.vel_limit[j];
+        s += clampf(fabsf(dof[2 * j + 1]) - lim * C.soft_dof_vel_limit, 0.0f, 1.0f);
+      }
+      r[T1_REW_DOF_VEL_LIMITS] = s;
     }
     // (a term with a zero scale has no reward function in the reference, legged_robot.py:351-384, so the state its
     // function keeps is not advanced either: feet_air_time / last_contacts here, feet_height / last_feet_z below)
-    r[7] = 0.0f;
-    if (C.reward_scales[7] != 0.0f) {  // 7 feet_air_time (mutates feet_air_time, last_contacts)
+    r[T1_REW_FEET_AIR_TIME] = 0.0f;
+    if (C.reward_scales[T1_REW_FEET_AIR_TIME] != 0.0f) {  // feet_air_time (mutates feet_air_time, last_contacts)
       float sm0 = ph.stance[0], sm1 = ph.stance[1];
       if (norm3(cmd[0], cmd[1], cmd[2]) < 0.05f) { sm0 = 1.0f; sm1 = 1.0f; }
       const bool filt0 = contact0 || sm0 > 0.0f || lc[0];
@@ -399,48 +414,53 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
       const float air1 = clampf(a1, 0.0f, 0.5f) * (first1 ? 1.0f : 0.0f);
       at[0] = a0 * (filt0 ? 0.0f : 1.0f);
       at[1] = a1 * (filt1 ? 0.0f : 1.0f);
-      r[7] = air0 + air1;
+      r[T1_REW_FEET_AIR_TIME] = air0 + air1;
     }
-    r[8] = 0.0f;
-    if (C.reward_scales[8] != 0.0f) {  // 8 feet_clearance (mutates feet_height, last_feet_z)
+    r[T1_REW_FEET_CLEARANCE] = 0.0f;
+    if (C.reward_scales[T1_REW_FEET_CLEARANCE] != 0.0f) {  // feet_clearance (mutates feet_height, last_feet_z)
       const float z0 = f0[2], z1 = f1[2];
       const float h0 = fh[0] + (z0 - lfz[0]), h1 = fh[1] + (z1 - lfz[1]);
       lfz[0] = z0; lfz[1] = z1;
       const float sw0 = 1.0f - ph.stance[0], sw1 = 1.0f - ph.stance[1];
       const float rp0 = (h0 > C.target_feet_height && h0 < C.target_feet_height_max) ? 1.0f : 0.0f;
       const float rp1 = (h1 > C.target_feet_height && h1 < C.target_feet_height_max) ? 1.0f : 0.0f;
-      r[8] = rp0 * sw0 + rp1 * sw1;
+      r[T1_REW_FEET_CLEARANCE] = rp0 * sw0 + rp1 * sw1;
       fh[0] = h0 * (contact0 ? 0.0f : 1.0f);
       fh[1] = h1 * (contact1 ? 0.0f : 1.0f);
     }
-    // 9 feet_contact_forces
-    r[9] = clampf(norm3(c0[0], c0[1], c0[2]) - C.max_contact_force, 0.0f, 400.0f) +
+    // feet_contact_forces
+    r[T1_REW_FEET_CONTACT_FORCES] = clampf(norm3(c0[0], c0[1], c0[2]) - C.max_contact_force, 0.0f, 400.0f) +
            clampf(norm3(c1[0], c1[1], c1[2]) - C.max_contact_force, 0.0f, 400.0f);
-    {  // 10 feet_contact_number
+    {  // feet_contact_number
       float sm0 = ph.stance[0], sm1 = ph.stance[1];
       if (stand) { sm0 = 1.0f; sm1 = 1.0f; }
       const float q0 = ((contact0 ? 1.0f : 0.0f) == sm0) ? 1.0f : -0.3f;
       const float q1 = ((contact1 ? 1.0f : 0.0f) == sm1) ? 1.0f : -0.3f;
-      r[10] = (q0 + q1) / 2.0f;
+      r[T1_REW_FEET_CONTACT_NUMBER] = (q0 + q1) / 2.0f;
     }
-    {  // 11 feet_distance, 15 knee_distance
+    {  // feet_distance, knee_distance
       const float fd = norm2(f0[0] - f1[0], f0[1] - f1[1]);
       const float kd = norm2(k0[0] - k1[0], k0[1] - k1[1]);
       const float fmn = clampf(fd - C.foot_min_dist, -0.5f, 0.0f), fmx = clampf(fd - C.foot_max_dist, 0.0f, 0.5f);
       const float kmn = clampf(kd - C.knee_min_dist, -0.5f, 0.0f), kmx = clampf(kd - C.knee_max_dist, 0.0f, 0.5f);
-      r[11] = (expf(-fabsf(fmn) * 100.0f) + expf(-fabsf(fmx) * 100.0f)) / 2.0f;
-      r[15] = (expf(-fabsf(kmn) * 100.0f) + expf(-fabsf(kmx) * 100.0f)) / 2.0f;
+      r[T1_REW_FEET_DISTANCE] = (expf(-fabsf(fmn) * 100.0f) + expf(-fabsf(fmx) * 100.0f)) / 2.0f;
+      r[T1_REW_KNEE_DISTANCE] = (expf(-fabsf(kmn) * 100.0f) + expf(-fabsf(kmx) * 100.0f)) / 2.0f;
     }
-    {  // 12 feet_rotation
+    {  // feet_rotation
       const float rot = fe[1] * fe[1] + fe[4] * fe[4];
       const float x = rot / 1.0f;
-      r[12] = 1.0f * expf(-(x * x));
+      r[T1_REW_FEET_ROTATION] = 1.0f * expf(-(x * x));
     }
-    {  // 13 foot_slip (rigid_state[..., 10:12] as in the reference)
+    r[T1_REW_FEET_STUMBLE] = 0.0f;
+    if (C.reward_scales[T1_REW_FEET_STUMBLE] != 0.0f) {  // feet_stumble (t1:937-940): a foot pushed sideways
+      const bool st0 = norm2(c0[0], c0[1]) > 5.0f * fabsf(c0[2]), st1 = norm2(c1[0], c1[1]) > 5.0f * fabsf(c1[2]);
+      r[T1_REW_FEET_STUMBLE] = (st0 || st1) ? 1.0f : 0.0f;
+    }
+    {  // foot_slip (rigid_state[..., 10:12] as in the reference)
       const float s0 = sqrtf(norm2(f0[10], f0[11])), s1 = sqrtf(norm2(f1[10], f1[11]));
-      r[13] = s0 * (contact0 ? 1.0f : 0.0f) + s1 * (contact1 ? 1.0f : 0.0f);
+      r[T1_REW_FOOT_SLIP] = s0 * (contact0 ? 1.0f : 0.0f) + s1 * (contact1 ? 1.0f : 0.0f);
     }
-    {  // 14 joint_pos (ref_dof_pos from the previous compute_observations)
+    {  // joint_pos (ref_dof_pos from the previous compute_observations)
       float s = 0.0f;
 #pragma unroll
       for (int j = 0; j < 12; ++j) {
@@ -449,9 +469,9 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
         s += d * d;
       }
       const float nr = sqrtf(s);
-      r[14] = stand ? 1.0f : expf(-2.0f * nr) - 0.2f * clampf(nr, 0.0f, 0.5f);
+      r[T1_REW_JOINT_POS] = stand ? 1.0f : expf(-2.0f * nr) - 0.2f * clampf(nr, 0.0f, 0.5f);
     }
-    {  // 16 low_speed
+    {  // low_speed
       const float sp = fabsf(blv[0]), cm = fabsf(cmd[0]);
       const bool low = sp < 0.5f * cm, high = sp > 1.2f * cm, ok = !(low || high);
       const bool mis = signf(blv[0]) != signf(cmd[0]);
@@ -460,14 +480,14 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
       if (high) v = 0.0f;
       if (ok) v = 1.2f;
       if (mis) v = -2.0f;
-      r[16] = v * (fabsf(cmd[0]) > 0.05f ? 1.0f : 0.0f);
+      r[T1_REW_LOW_SPEED] = v * (fabsf(cmd[0]) > 0.05f ? 1.0f : 0.0f);
     }
-    {  // 17 orientation
+    {  // orientation
       const float qm = expf(-(fabsf(be[0]) + fabsf(be[1])) * 10.0f);
       const float o = expf(-norm2(pg[0], pg[1]) * 20.0f);
-      r[17] = (qm + o) / 2.0f;
+      r[T1_REW_ORIENTATION] = (qm + o) / 2.0f;
     }
-    {  // 18 stand_still
+    {  // stand_still
       const int idx[8] = {0, 1, 2, 3, 5, 6, 7, 8};
       const float w[10] = {2.0f, 2.0f, 1.0f, 1.0f, 1.0f, 2.0f, 2.0f, 1.0f, 1.0f, 1.0f};
       float s = 0.0f;
@@ -479,32 +499,40 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
       const float e8 = fe[1] * w[8], e9 = fe[4] * w[9];
       s += e8 * e8;
       s += e9 * e9;
-      r[18] = stand ? expf(-s) : 0.0f;
+      r[T1_REW_STAND_STILL] = stand ? expf(-s) : 0.0f;
     }
-    {  // 19 torques
+    r[T1_REW_STAND_SYSMETRY] = 0.0f;
+    if (C.reward_scales[T1_REW_STAND_SYSMETRY] != 0.0f) {  // stand_sysmetry (t1:917-925): left vs right leg, standing
+      float s = 0.0f;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { const float d = dof[2 * k] - dof[2 * (5 + k)]; s += d * d; }
+      r[T1_REW_STAND_SYSMETRY] = stand ? expf(-s) : 0.0f;
+    }
+    r[T1_REW_TERMINATION] = 0.0f;  // not in the clipped sum: added after the clip below
+    {  // torques
       float s = 0.0f;
 #pragma unroll
       for (int j = 0; j < 12; ++j) s += tq[j] * tq[j];
-      r[19] = s;
+      r[T1_REW_TORQUES] = s;
     }
-    {  // 20 track_vel_hard
+    {  // track_vel_hard
       const float le = norm2(cmd[0] - blv[0], cmd[1] - blv[1]);
       const float ae = fabsf(cmd[2] - bav[2]);
-      r[20] = (expf(-le * 10.0f) + expf(-ae * 10.0f)) / 2.0f - 0.2f * (le + ae);
+      r[T1_REW_TRACK_VEL_HARD] = (expf(-le * 10.0f) + expf(-ae * 10.0f)) / 2.0f - 0.2f * (le + ae);
     }
-    {  // 21 tracking_ang_vel
+    {  // tracking_ang_vel
       const float d = cmd[2] - bav[2];
-      r[21] = stand ? expf(-fabsf(d) * (C.tracking_sigma * 2.0f)) : expf(-(d * d) * C.tracking_sigma);
+      r[T1_REW_TRACKING_ANG_VEL] = stand ? expf(-fabsf(d) * (C.tracking_sigma * 2.0f)) : expf(-(d * d) * C.tracking_sigma);
     }
-    {  // 22 tracking_lin_vel
+    {  // tracking_lin_vel
       const float dx = cmd[0] - blv[0], dy = cmd[1] - blv[1];
-      r[22] = stand ? expf(-(fabsf(dx) + fabsf(dy)) * (C.tracking_sigma * 2.0f))
+      r[T1_REW_TRACKING_LIN_VEL] = stand ? expf(-(fabsf(dx) + fabsf(dy)) * (C.tracking_sigma * 2.0f))
                     : expf(-(dx * dx + dy * dy) * C.tracking_sigma);
     }
-    {  // 23 vel_mismatch_exp
+    {  // vel_mismatch_exp
       const float lm = expf(-(blv[2] * blv[2]) * 10.0f);
       const float am = expf(-norm2(bav[0], bav[1]) * 5.0f);
-      r[23] = (lm + am) / 2.0f;
+      r[T1_REW_VEL_MISMATCH_EXP] = (lm + am) / 2.0f;
     }
   }
   T1_PROF_MARK(18);
@@ -512,12 +540,20 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
   if constexpr (PART != POST_A_STATE) {
 #pragma unroll
     for (int k = 0; k < T1_NREW; ++k) {
+      if (k == T1_REW_TERMINATION) continue;
       const float v = r[k] * C.reward_scales[k];
       rew = rew + v;
       esum[k] = esum[k] + v;
-      contrib[k] = do_reset ? esum[k] : 0.0f;
     }
     if (C.only_positive_rewards) rew = fmaxf(rew, 0.0f);
+    // termination (t1:894-896): reset_buf * ~time_out_buf, added after the clip (legged_robot.py:676-680)
+    if (C.reward_scales[T1_REW_TERMINATION] != 0.0f) {
+      const float v = ((do_reset && !tout) ? 1.0f : 0.0f) * C.reward_scales[T1_REW_TERMINATION];
+      rew = rew + v;
+      esum[T1_REW_TERMINATION] = esum[T1_REW_TERMINATION] + v;
+    }
+#pragma unroll
+    for (int k = 0; k < T1_NREW; ++k) contrib[k] = do_reset ? esum[k] : 0.0f;
   }
   T1_PROF_MARK(19);
   // ---- outputs
@@ -571,7 +607,7 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
         for (int k = 0; k <= T1_NREW; ++k) __hip_atomic_store(ep_row + k, 0.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     } else
-      wave_atomic_add_n(B.ep_accum, part);  // ep_accum[0..23] episode sums, [24] reset count
+      wave_atomic_add_n(B.ep_accum, part);  // ep_accum[0..T1_NREW) episode sums, [T1_ACC_COUNT] reset count
   }
   X.el = el;
   X.pl = pl;

@@ -25,11 +25,15 @@ from ..utils.helpers import class_to_dict
 from ..utils.terrain import Terrain
 from ..utils.urdf import load_model, self_capsules
 
+# every _reward_* of the reference's t1_dh_stand_env.py, in the kernels' index order (include/t1env.h T1_REW_*); the
+# four listed last have scale 0 in DHT1StandCfg
 REWARD_NAMES = sorted(["action_smoothness", "base_acc", "base_height", "collision", "default_joint_pos", "dof_acc",
                        "dof_vel", "feet_air_time", "feet_clearance", "feet_contact_forces", "feet_contact_number",
                        "feet_distance", "feet_rotation", "foot_slip", "joint_pos", "knee_distance", "low_speed",
                        "orientation", "stand_still", "torques", "track_vel_hard", "tracking_ang_vel",
-                       "tracking_lin_vel", "vel_mismatch_exp"])
+                       "tracking_lin_vel", "vel_mismatch_exp",
+                       "dof_vel_limits", "feet_stumble", "stand_sysmetry", "termination"])
+assert len(REWARD_NAMES) == _lib.NREW
 GAIT_KINDS = {"walk_omnidirectional": 0, "stand": 1, "walk_sagittal": 2, "walk_lateral": 3, "rotate": 4}
 
 # Solver constants of the compliant contact / soft limit model (PhysX TGS is unpinned).
@@ -166,6 +170,21 @@ def check_supported(cfg):
         # HIP dynamics applies the base force only (ext_torque_max = 0 in DHT1StandCfg, t1_dh_stand_config.py:201)
         raise NotImplementedError("domain_rand.ext_torque_max != 0: external base torques are not applied by the HIP "
                                   "dynamics (t1_dh_stand uses 0)")
+    active_reward_scales(cfg)
+
+
+def active_reward_scales(cfg):
+    """The non-zero entries of cfg.rewards.scales (legged_robot.py:351-384 drops the zero ones).  A name without a HIP
+    kernel raises; so does dof_vel_limits without rewards.soft_dof_vel_limit, which neither reference config defines
+    and the reference's _reward_dof_vel_limits reads (t1_dh_stand_env.py:946, an AttributeError there too)."""
+    scales = {k: v for k, v in class_to_dict(cfg.rewards.scales).items() if v != 0}
+    unknown = set(scales) - set(REWARD_NAMES)
+    if unknown:
+        raise NotImplementedError(f"reward terms without a HIP kernel: {sorted(unknown)}")
+    if "dof_vel_limits" in scales and not hasattr(cfg.rewards, "soft_dof_vel_limit"):
+        raise AttributeError("rewards.scales.dof_vel_limits is set but rewards.soft_dof_vel_limit is not: the term "
+                             "penalises |dof_vel| above dof_vel_limits * soft_dof_vel_limit and has no default")
+    return scales
 
 
 class T1DHStandEnv(VecEnv):
@@ -217,10 +236,7 @@ class T1DHStandEnv(VecEnv):
         dr = cfg.domain_rand
         self.push_interval = np.ceil(dr.push_interval_s / self.dt)
         self.ext_force_interval = np.ceil(dr.ext_force_interval_s / self.dt)
-        scales = {k: v for k, v in class_to_dict(cfg.rewards.scales).items() if v != 0}
-        unknown = set(scales) - set(REWARD_NAMES)
-        if unknown:
-            raise NotImplementedError(f"reward terms without a HIP kernel: {sorted(unknown)}")
+        scales = active_reward_scales(cfg)
         self.reward_scales = {k: v * self.dt for k, v in scales.items()}
         self.reward_names = [k for k in REWARD_NAMES if k in self.reward_scales]
         self.common_step_counter = 0
@@ -388,6 +404,8 @@ class T1DHStandEnv(VecEnv):
         for k in ("base_height_target", "foot_min_dist", "foot_max_dist", "knee_min_dist", "knee_max_dist",
                   "target_feet_height", "target_feet_height_max", "tracking_sigma", "max_contact_force"):
             setattr(c, k, getattr(r, k))
+        # read by dof_vel_limits alone, and required when that term is on (active_reward_scales)
+        c.soft_dof_vel_limit = float(r.soft_dof_vel_limit) if "dof_vel_limits" in self.reward_scales else 0.0
         for i, g in enumerate(cfg.commands.gait):   # (3 known gaits: check_supported)
             c.gait_kind[i] = GAIT_KINDS[g]
             c.gait_time_range[i][0], c.gait_time_range[i][1] = cfg.commands.gait_time_range[g]
@@ -586,7 +604,7 @@ class T1DHStandEnv(VecEnv):
             if needs_curriculum:
                 idx = REWARD_NAMES.index("tracking_lin_vel")
                 acc = self._ep_accum.cpu()
-                self._command_curriculum(float(acc[idx]), float(acc[24]))
+                self._command_curriculum(float(acc[idx]), float(acc[_lib.ACC_COUNT]))
                 a = self._args(self.common_step_counter, ext_call, ext_first, push_call)
             _lib.check(lib.t1env_step_reset_and_observe(h, _lib.C.byref(a), s), "t1env_step_reset_and_observe")
             if self.measure_heights:
@@ -608,7 +626,7 @@ class T1DHStandEnv(VecEnv):
                 ex = self._extras_ring[r]
                 ep = {"rew_" + k: ex[REWARD_NAMES.index(k)] for k in self.reward_names}
                 if self.mesh_type == "trimesh":
-                    ep["terrain_level"] = ex[24]
+                    ep["terrain_level"] = ex[_lib.EX_TERRAIN_LEVEL]
                 self._ep_dicts.append(ep)
         ep = self._ep_dicts[slot]
         if self.cfg.commands.curriculum:
