@@ -18,6 +18,9 @@ CPU here (the reference's device): measured, the updated weights come out bit-id
 losses within 2e-7 (the build sums them on the device).  The same replay runs on the MI355X (the HIP fp32 update
 kernels: three-part bf16 split weight gradients, the packed conv, hipBLASLt or the HIP GEMM) in the gpu test, with the
 same bounds (measured: losses within 2.5e-5, weight-delta abs-sums within 1.1e-6).
+
+The gradients themselves, before and after the clip, are pinned in tests/test_ppo_grads.py (the host build against the
+reference's recorded gradients and an fp64 restatement) and tests/test_gpu_ppo_grads.py (the device update against fp64).
 """
 import numpy as np
 import pytest
