@@ -42,7 +42,7 @@ int t1policy_conv1d_forward_packed(const float* x, const void* frag, const float
  * input is its own hi part with a zero lo part, so the result equals t1policy_conv1d_forward_packed on the widened x up
  * to fp32 summation order (the lo.hi products it drops are exact zeros; within 1e-5 * (1 + |y|) of an fp64 conv of the
  * widened x, tests/test_gpu_policy_fp16_obs.py).  x 4-byte aligned (a 2-byte-aligned base returns -1);
- * batch * channels * length * 2 < 2^31.  T1POLICY_CONV=regs has no fp16 instance (the default kernel runs). */
+ * batch * channels * length * 2 < 2^31. */
 int t1policy_conv1d_forward_packed_h(const void* x, const void* frag, const float* bias, float* y, int batch,
                                      int channels, int length, int out_channels, int kernel, int stride, void* stream);
 

@@ -70,19 +70,17 @@ def test_conv1_bf16_refuses_other_shapes():
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
 @pytest.mark.parametrize("rows,cols", [(49152, 256), (49152, 3), (777, 768)])
-def test_bias_colsum_matches_fp64(rows, cols, dtype, monkeypatch):
-    """The update's Linear bias gradients (dh_policy.bias_grad, t1policy_colsum): fp32 sums in a fixed order, within
-    fp32 summation error of an fp64 sum, the same bits on a second call."""
-    from ti5_isaacgym_amd.algo import dh_policy
-    from ti5_isaacgym_amd.algo.dh_policy import bias_grad
-    monkeypatch.setattr(dh_policy, "BIAS_COLSUM", True)   # the opt-in kernel (torch's sum is the default)
+def test_bias_colsum_matches_fp64(rows, cols, dtype):
+    """A Linear bias gradient as the HIP column sum (dh_policy.colsum, t1policy_colsum): fp32 sums in a fixed order,
+    within fp32 summation error of an fp64 sum, the same bits on a second call."""
+    from ti5_isaacgym_amd.algo.dh_policy import colsum
     g = torch.Generator(device=DEV).manual_seed(rows + cols)
     gy = torch.randn(rows, cols, device=DEV, generator=g).to(dtype)
-    out = bias_grad(gy)
+    out = colsum(gy)
     assert out.dtype == torch.float32 and out.shape == (cols,)
     ref = gy.double().sum(0)
     torch.testing.assert_close(out.double(), ref, rtol=1e-5, atol=1e-3)
-    assert torch.equal(bias_grad(gy), out)
+    assert torch.equal(colsum(gy), out)
 
 
 @pytest.mark.parametrize("slices,shape", [(24, (512, 302)), (24, (3, 64)), (5, (7, 13)), (1, (768, 219)), (9, (128, 96))])
@@ -160,7 +158,7 @@ def test_conv1_f32_weight_gradient_matches_fp64(n):
 
 def test_history_encoder_fp32_update_uses_the_hip_conv(monkeypatch):
     """Under autograd in fp32 the history encoder's first conv takes conv1d_train_f32 (no unfold), and the encoder's
-    output and weight gradients match the unfold + GEMM path (T1_CONV1_TRAIN off) within fp32 summation order."""
+    output and weight gradients match the unfold + GEMM path (conv1d_train_f32 refusing) within fp32 summation order."""
     from ti5_isaacgym_amd.algo import dh_policy
     torch.manual_seed(1)
     enc = dh_policy._history_encoder(66, 47, [32, 16], [6, 4], [3, 2], 16).to(DEV)
@@ -173,7 +171,8 @@ def test_history_encoder_fp32_update_uses_the_hip_conv(monkeypatch):
     g1 = [p.grad.clone() for p in enc.parameters()]
     assert calls, "the fp32 HIP conv was not used"
     enc.zero_grad()
-    monkeypatch.setattr(dh_policy, "CONV1_TRAIN", False)
+    # its documented refusal (None): HistoryEncoder keeps unfold + GEMM (conv1d_as_gemm)
+    monkeypatch.setattr(dh_policy, "conv1d_train_f32", lambda *a: None)
     out2 = enc(x)
     out2.square().sum().backward()
     torch.testing.assert_close(out, out2, rtol=1e-5, atol=1e-6)

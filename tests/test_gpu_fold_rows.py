@@ -37,13 +37,22 @@ def test_history_encoder_grads_unchanged_by_the_gather(monkeypatch):
     ac = dh_policy.ActorCriticDH(235, 47, 219, 12).to(DEV)
     obs = torch.randn(2048, 66, 47, device=DEV).to(torch.bfloat16)
 
-    def grads(flag):
-        monkeypatch.setattr(dh_policy, "FOLD_ROWS", flag)
+    def grads():
         ac.zero_grad(set_to_none=True)
         with torch.autocast(device_type="cuda", dtype=torch.bfloat16):
             code = ac.long_history(obs)
         code.float().square().sum().backward()
         return [p.grad.clone() for p in ac.long_history.parameters()]
 
-    a, b = grads(True), grads(False)
+    class TorchUnfold:
+        """The same rows by torch's unfold, so autograd's unfold backward gives the input gradient."""
+
+        @staticmethod
+        def apply(x, k, st):
+            win = x.unfold(1, k, st)
+            return win.reshape(win.shape[0] * win.shape[1], win.shape[2] * k)
+
+    a = grads()
+    monkeypatch.setattr(dh_policy, "_UnfoldRows", TorchUnfold)
+    b = grads()
     assert all(torch.equal(u, v) for u, v in zip(a, b))

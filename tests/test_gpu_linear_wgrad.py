@@ -72,17 +72,18 @@ def test_linear_backward_uses_the_kernel_under_bf16_autocast(monkeypatch):
     x = torch.randn(49152, 302, device=DEV).to(torch.bfloat16)
     g = torch.randn(49152, 512, device=DEV).to(torch.bfloat16) * 0.01
 
-    def grads(flag):
-        monkeypatch.setattr(dh_policy, "LINEAR_WGRAD", flag)
-        lin.weight.grad = lin.bias.grad = None
-        with torch.autocast(device_type="cuda", dtype=torch.bfloat16):
-            y = lin(x)
-        y.backward(g)
-        return lin.weight.grad.clone(), lin.bias.grad.clone()
-
-    gw, gb = grads(True)
+    calls = []
+    real = dh_policy.linear_wgrad_bf16
+    monkeypatch.setattr(dh_policy, "linear_wgrad_bf16", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    with torch.autocast(device_type="cuda", dtype=torch.bfloat16):
+        y = lin(x)
+    y.backward(g)
+    assert calls, "the backward did not take the bf16 wgrad kernel"
+    gw, gb = lin.weight.grad.clone(), lin.bias.grad.clone()
     _check(gw, gb, g, x)
-    gw0, gb0 = grads(False)
+    # the split-K path on the same operands: the batched GEMM + slice sum, torch's bias sum widened
+    gw0 = dh_policy.wgrad_splitk(g, x)
+    gb0 = g.sum(0).float()
     torch.testing.assert_close(gw, gw0, rtol=1e-2, atol=1e-3 * gw0.abs().max().item())
     torch.testing.assert_close(gb, gb0, rtol=1e-2, atol=1e-3 * gb0.abs().max().item())
 
@@ -100,7 +101,7 @@ def test_linear_wgrad_rejects_bad_arguments():
 
 
 def test_linear_wgrad_accumulates_into_existing_grads(monkeypatch):
-    """into=: the sums ADDED to existing fp32 gradients; through autograd (GRAD_DIRECT, the PPO update's bucket views) a
+    """into=: the sums ADDED to existing fp32 gradients; through autograd (direct_grad_accumulation, the PPO update's bucket views) a
     preset .grad ends as the same bits as autograd's own accumulation of the returned gradient."""
     from ti5_isaacgym_amd.algo import dh_policy
     gy, x = _operands(3000, 96, 130, 11)
@@ -270,7 +271,7 @@ def test_linear_wgrad_f32_strided_x_read_in_place(rows, M, N, wide):
 
 def test_linear_fp32_forward_and_input_gradient_use_the_gemm(monkeypatch):
     """In fp32 under autograd the Linear's forward and input gradient come from t1policy_gemm_nt_f32, within fp32
-    summation order of torch's; T1 GEMM_F32 off gives torch's."""
+    summation order of torch's."""
     from ti5_isaacgym_amd.algo import dh_policy
     calls = []
     real = dh_policy.gemm_nt_f32
@@ -287,9 +288,9 @@ def test_linear_fp32_forward_and_input_gradient_use_the_gemm(monkeypatch):
     torch.testing.assert_close(x.grad, gy @ lin.weight, rtol=1e-5, atol=1e-6)
 
 
-def test_mlp_fp32_fused_node_matches_layer_by_layer(monkeypatch):
+def test_mlp_fp32_fused_node_matches_layer_by_layer():
     """The fp32 update's MLP as one autograd node (_MlpF32: ELU fused into the forward GEMMs, ELU's derivative into the
-    input-gradient GEMMs) against the layer-by-layer path (T1_MLP_F32 off): outputs and every gradient within fp32
+    input-gradient GEMMs) against the layer-by-layer path (nn.Sequential's forward): outputs and every gradient within fp32
     summation order, and inside direct_grad_accumulation() the weight gradients added into the existing .grad."""
     from ti5_isaacgym_amd.algo import dh_policy
     torch.manual_seed(11)
@@ -298,22 +299,21 @@ def test_mlp_fp32_fused_node_matches_layer_by_layer(monkeypatch):
     x = torch.randn(6000, 302, device=DEV, requires_grad=True)
     go = torch.randn(6000, 12, device=DEV)
 
-    def run(flag):
-        monkeypatch.setattr(dh_policy, "MLP_F32", flag)
+    def run(forward):
         mlp.zero_grad(set_to_none=True)
         x.grad = None
-        y = mlp(x)
+        y = forward(x)
         y.backward(go)
         return y.detach().clone(), x.grad.clone(), [p.grad.clone() for p in mlp.parameters()]
 
-    y1, gx1, g1 = run(True)
-    y0, gx0, g0 = run(False)
+    y1, gx1, g1 = run(mlp)
+    # layer by layer: nn.Sequential's own forward, every Linear its own _LinearSplitK node and torch's ELU between
+    y0, gx0, g0 = run(lambda v: torch.nn.Sequential.forward(mlp, v))
     torch.testing.assert_close(y1, y0, rtol=1e-5, atol=1e-5)
     torch.testing.assert_close(gx1, gx0, rtol=1e-4, atol=1e-5 * gx0.abs().max().item())
     for a, b in zip(g1, g0):
         torch.testing.assert_close(a, b, rtol=1e-4, atol=1e-5 * b.abs().max().item())
     # direct accumulation: a second backward inside the context doubles every .grad
-    monkeypatch.setattr(dh_policy, "MLP_F32", True)
     for p, a in zip(mlp.parameters(), g1):
         p.grad = a.clone()
     with dh_policy.direct_grad_accumulation():

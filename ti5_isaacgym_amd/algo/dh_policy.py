@@ -15,49 +15,42 @@ Same architecture, parameter names and initialisation as the reference, so its c
 through PyTorch-ROCm; the per-step inference batch is every env on the rank.
 """
 import contextlib
-import os
 
 import torch
 import torch.nn as nn
 from torch.distributions import Normal
 
 
-# rows of the batch (K of the weight-gradient GEMM) per split-K slice (T1_SPLITK_ROWS: A/B)
-def _splitk_rows(v):
-    """T1_SPLITK_ROWS, checked at import (a bad value would otherwise fail deep inside a backward pass)."""
-    try:
-        r = int(v)
-    except ValueError:
-        r = 0
-    if r <= 0:
-        raise ValueError(f"T1_SPLITK_ROWS must be a positive integer, got {v!r}")
-    return r
+def _load():
+    from .. import _lib
+    return _lib.load()
 
 
-SPLITK_ROWS = _splitk_rows(os.environ.get("T1_SPLITK_ROWS", "2048"))
-# bf16 split-K partial products returned in fp32 by the GEMM itself (T1_WGRAD_OUT_F32=0: the bf16 partials widened
-# afterwards, the round-2 path; A/B)
-WGRAD_OUT_F32 = os.environ.get("T1_WGRAD_OUT_F32", "1") != "0"
+def _call(fn, *args, refusals=()):
+    """The HIP library's entry `fn` on args: its return code where that is 0 or one of `refusals` (1 / -1: no
+    instance for these arguments, nothing launched -- for a caller with another way), a RuntimeError for any other."""
+    rc = getattr(_load(), fn)(*args)
+    if rc != 0 and rc not in refusals:
+        raise RuntimeError(f"{fn} failed (rc={rc})")
+    return rc
 
 
-# the split-K partial products summed by the HIP slice sum (t1policy_slice_sum, slices in order) on the device;
-# T1_SLICE_SUM=0: torch's part.sum(0) (A/B)
-SLICE_SUM = os.environ.get("T1_SLICE_SUM", "1") != "0"
+def _stream(t):
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+# rows of the batch (K of the weight-gradient GEMM) per split-K slice
+SPLITK_ROWS = 2048
 
 
 def slice_sum(part):
     """part.sum(0) of the (S, M, N) split-K partial products: on the device the HIP slice sum (fp32, s = 0, 1, ... in
     order: one HBM pass instead of torch's dim-0 reduction kernel), on the host or for other dtypes torch's."""
-    if not (part.is_cuda and SLICE_SUM and part.dtype == torch.float32):
+    if not (part.is_cuda and part.dtype == torch.float32):
         return part.sum(0)
-    from .. import _lib
-    lib = _lib.load()
     part = part.contiguous()
     out = torch.empty(part.shape[1:], device=part.device, dtype=torch.float32)
-    rc = lib.t1policy_slice_sum(part.data_ptr(), part.shape[0], out.numel(), out.data_ptr(),
-                                torch.cuda.current_stream(part.device).cuda_stream)
-    if rc != 0:
-        raise RuntimeError(f"t1policy_slice_sum failed (rc={rc})")
+    _call("t1policy_slice_sum", part.data_ptr(), part.shape[0], out.numel(), out.data_ptr(), _stream(part))
     return out
 
 
@@ -82,7 +75,7 @@ def wgrad_splitk(gy, x):
         with torch.autocast(device_type="cuda", enabled=False):
             return wgrad_splitk(wide(gy), wide(x))
     a, b = gy[:c].view(S, SPLITK_ROWS, M).transpose(1, 2), x[:c].view(S, SPLITK_ROWS, -1)
-    if WGRAD_OUT_F32 and gy.is_cuda and gy.dtype in (torch.bfloat16, torch.float16):
+    if gy.is_cuda and gy.dtype in (torch.bfloat16, torch.float16):
         # bf16 operands, fp32 partial products straight from the GEMM (aten::bmm.dtype): no bf16 rounding of the
         # 2,048-row partial sums and no widening copy of them.  An fp32 saved input is rounded to the gradient's dtype
         # first, as autocast's bmm would (the once-per-update obs cast stays bit-identical to the per-minibatch one)
@@ -94,43 +87,33 @@ def wgrad_splitk(gy, x):
     return gw
 
 
-# the Linear bias gradients as the HIP column sum (opt-in, T1_BIAS_COLSUM=1): measured slower than torch's dim-0 sum
-# in the graphed update (bf16 update 39.8 vs 38.1 ms per iteration, profiles/r04q3_*), so torch's stays the default
-BIAS_COLSUM = os.environ.get("T1_BIAS_COLSUM", "0") == "1"
-
-
-def bias_grad(gy):
-    """gy.sum(0) of a (K, M) gradient: on the device the HIP column sum (t1policy_colsum: fp32 accumulation in a fixed
-    order, an fp32 result for the fp32 bias), on the host torch's."""
-    if not (gy.is_cuda and BIAS_COLSUM and gy.dim() == 2 and gy.dtype in (torch.bfloat16, torch.float32)):
-        return gy.sum(0)
-    from .. import _lib
-    lib = _lib.load()
+def colsum(gy):
+    """gy.sum(0) of a (K, M) bf16 / fp32 device gradient as the HIP column sum (t1policy_colsum: fp32 accumulation in a
+    fixed order, an fp32 result).  Not on the update's path: torch's dim-0 sum measured faster in the graphed update
+    (bf16 update 38.1 vs 39.8 ms per iteration, profiles/r04q3_*), so the Linear bias gradients are gy.sum(0)."""
+    if not (gy.is_cuda and gy.dim() == 2 and gy.dtype in (torch.bfloat16, torch.float32)):
+        raise ValueError(f"colsum: a 2-D bf16 / fp32 device tensor, got {tuple(gy.shape)} {gy.dtype} on {gy.device}")
     gy = gy.contiguous()
     K, M = gy.shape
-    ws = torch.empty(lib.t1policy_colsum_workspace_bytes(K, M), device=gy.device, dtype=torch.uint8)
+    ws = torch.empty(_load().t1policy_colsum_workspace_bytes(K, M), device=gy.device, dtype=torch.uint8)
     out = torch.empty(M, device=gy.device, dtype=torch.float32)
-    rc = lib.t1policy_colsum(gy.data_ptr(), gy.element_size(), K, M, ws.data_ptr(), out.data_ptr(),
-                             torch.cuda.current_stream(gy.device).cuda_stream)
-    if rc != 0:
-        raise RuntimeError(f"t1policy_colsum failed (rc={rc})")
+    _call("t1policy_colsum", gy.data_ptr(), gy.element_size(), K, M, ws.data_ptr(), out.data_ptr(), _stream(gy))
     return out
 
 
-# ... added by that kernel straight into an existing .grad of the layer's leaf parameters (T1_GRAD_DIRECT=0: returned
-# to autograd, which adds them, A/B).  Only inside direct_grad_accumulation(), which DHPPO opens around its own
+# The Linear weight + bias gradients of the wgrad kernels below are added straight into an existing .grad of the
+# layer's leaf parameters, but only inside direct_grad_accumulation(), which DHPPO opens around its own
 # loss.backward(): anywhere else (torch.autograd.grad, backward(inputs=...), a caller's own backward) the gradients go
 # back through autograd, so what autograd returns and which .grad it touches are exactly torch's.
-GRAD_DIRECT = os.environ.get("T1_GRAD_DIRECT", "1") != "0"
-# a module flag, not a contextvar: autograd runs a CUDA node's backward on its device worker thread, which does not
+# A module flag, not a contextvar: autograd runs a CUDA node's backward on its device worker thread, which does not
 # see the calling thread's context variables
 _DIRECT_GRAD = [False]
 
 
 @contextlib.contextmanager
 def direct_grad_accumulation(enabled=True):
-    """Within the block, a backward() of _LinearSplitK under the bf16 update may add its weight / bias gradients straight
-    into the leaf parameters' existing fp32 .grad (returning None to autograd for them).  Valid only around a plain
+    """Within the block, a backward() of _LinearSplitK / _MlpF32 may add its weight / bias gradients straight into the
+    leaf parameters' existing fp32 .grad (returning None to autograd for them).  Valid only around a plain
     loss.backward() that accumulates into every parameter's .grad -- DHPPO's minibatch step."""
     prev = _DIRECT_GRAD[0]
     _DIRECT_GRAD[0] = bool(enabled)
@@ -138,14 +121,20 @@ def direct_grad_accumulation(enabled=True):
         yield
     finally:
         _DIRECT_GRAD[0] = prev
-# the bf16 update's Linear weight + bias gradients as one HIP MFMA kernel (t1policy_linear_wgrad_bf16); T1_LINEAR_WGRAD=0:
-# the split-K batched GEMM + slice sum + torch's bias sum (A/B)
-LINEAR_WGRAD = os.environ.get("T1_LINEAR_WGRAD", "1") != "0"
 
 
-# the fp32 update's Linear weight + bias gradients as the HIP three-part-split kernel (t1policy_linear_wgrad_f32);
-# T1_LINEAR_WGRAD_F32=0: the split-K batched GEMM + slice sum + bias sum (A/B)
-LINEAR_WGRAD_F32 = os.environ.get("T1_LINEAR_WGRAD_F32", "1") != "0"
+def _grad_into(wl, bl, need_b):
+    """The into= pair of the wgrad kernels -- the existing .grad of the leaf weight wl and, where the bias gradient is
+    needed, of the leaf bias bl -- when the kernel may add there: inside direct_grad_accumulation(), both leaves with
+    an fp32 .grad (the PPO update's views into the all-reduce bucket), the weight's contiguous.  Else None."""
+    if not (_DIRECT_GRAD[0] and wl is not None and wl.grad is not None and wl.grad.dtype == torch.float32
+            and wl.grad.is_contiguous()):
+        return None
+    if not need_b:
+        return wl.grad, None
+    if bl is None or bl.grad is None or bl.grad.dtype != torch.float32:
+        return None
+    return wl.grad, bl.grad
 
 
 def linear_wgrad_bf16(gy, x, need_bias=True, into=None):
@@ -172,17 +161,11 @@ def linear_wgrad_f32(gy, x, need_bias=True, into=None):
     return _linear_wgrad("t1policy_linear_wgrad_f32", gy, x.contiguous(), need_bias, into)
 
 
-# the fp32 update's Linear forward / input-gradient GEMMs as the HIP three-part-split GEMM (t1policy_gemm_nt_f32);
-# T1_GEMM_F32=0: hipBLASLt's fp32 addmm / mm (A/B)
-GEMM_F32 = os.environ.get("T1_GEMM_F32", "1") != "0"
-
-
 def gemm_nt_f32(a, b, bias=None, act=0, aux=None):
     """a (R, K) @ b (N, K)^T (+ bias) in fp32 on the matrix cores (t1policy_gemm_nt_f32: each value in three bf16 parts,
     fp32-class sums in k order), then act=1: ELU (alpha 1); act=2: times ELU's derivative at the ELU outputs aux (R, N)
-    (1 where aux > 0, else aux + 1) -- the backward of a Linear whose input came out of an ELU.  Device fp32 tensors."""
-    from .. import _lib
-    lib = _lib.load()
+    (1 where aux > 0, else aux + 1) -- the backward of a Linear whose input came out of an ELU.  Device fp32 tensors:
+    the fp32 update's Linear forward / input-gradient GEMMs."""
     R, K = a.shape
     N = b.shape[0]
     if b.shape[1] != K or a.dtype != torch.float32 or b.dtype != torch.float32:
@@ -212,18 +195,20 @@ def gemm_nt_f32(a, b, bias=None, act=0, aux=None):
     if act == 2:
         aux = aux.contiguous()
         xp = aux.data_ptr()
-    st = torch.cuda.current_stream(a.device).cuda_stream
+    st = _stream(a)
     lda = a.stride(0)
     strided = not (lda == K and ldb == K and not b_kn)
     rc = -1
     if strided and K > 0:
-        rc = lib.t1policy_gemm_f32(a.data_ptr(), lda, b.data_ptr(), ldb, b_kn, bp, xp, out.data_ptr(), R, N, K, act, st)
+        rc = _call("t1policy_gemm_f32", a.data_ptr(), lda, b.data_ptr(), ldb, b_kn, bp, xp, out.data_ptr(), R, N, K, act,
+                   st, refusals=(-1,))
         if rc == -1:
             # refused: the in-place entry has the staged kernel only, whose 32-bit offsets take operands below 1 GiB
             # (strides included) -- copy, and let the contiguous entry pick its kernel (the first form from 1 GiB on)
             a, b = a.contiguous(), b.contiguous()
     if rc == -1 and K > 0:
-        rc = lib.t1policy_gemm_nt_f32(a.data_ptr(), b.data_ptr(), bp, xp, out.data_ptr(), R, N, K, act, st)
+        rc = _call("t1policy_gemm_nt_f32", a.data_ptr(), b.data_ptr(), bp, xp, out.data_ptr(), R, N, K, act, st,
+                   refusals=(-1,))
     if rc == -1 and (K == 0 or R * max(K, N) >= 2 ** 31):
         # past the kernels' 2^31-element limit (or nothing to sum): torch's GEMM and the same epilogues in torch
         a, b = a.contiguous(), b.contiguous()
@@ -234,15 +219,13 @@ def gemm_nt_f32(a, b, bias=None, act=0, aux=None):
             y = y * torch.where(aux > 0, torch.ones_like(aux), aux + 1.0)
         return y
     if rc != 0:
-        raise RuntimeError(f"t1policy_gemm_f32 failed (rc={rc}; R {R}, N {N}, K {K}, lda {lda}, ldb {ldb}, b_kn {b_kn})")
+        raise RuntimeError(f"t1policy_gemm_f32 refused (rc={rc}; R {R}, N {N}, K {K}, lda {lda}, ldb {ldb}, b_kn {b_kn})")
     return out
 
 
 def _linear_wgrad(fn, gy, x, need_bias, into, ldx=None, may_refuse=False):
     """may_refuse: None instead of a RuntimeError when the entry refuses the arguments (rc -1, before any launch: the
     gradients of into= are untouched), for a caller with another way to the same sums."""
-    from .. import _lib
-    lib = _lib.load()
     K, M = gy.shape
     N = x.shape[1]
     if x.shape[0] != K:
@@ -252,7 +235,7 @@ def _linear_wgrad(fn, gy, x, need_bias, into, ldx=None, may_refuse=False):
             return into
         return (torch.zeros(M, N, device=gy.device, dtype=torch.float32),
                 torch.zeros(M, device=gy.device, dtype=torch.float32) if need_bias else None)
-    nbytes = lib.t1policy_linear_wgrad_workspace_bytes(K, M, N)
+    nbytes = _load().t1policy_linear_wgrad_workspace_bytes(K, M, N)
     if nbytes <= 0:
         raise RuntimeError(f"t1policy_linear_wgrad_workspace_bytes failed ({nbytes})")
     ws = torch.empty(nbytes, device=gy.device, dtype=torch.uint8)
@@ -266,19 +249,14 @@ def _linear_wgrad(fn, gy, x, need_bias, into, ldx=None, may_refuse=False):
         gw = torch.empty(M, N, device=gy.device, dtype=torch.float32)
         gb = torch.empty(M, device=gy.device, dtype=torch.float32) if need_bias else None
     rows_args = (K, M, N) if ldx is None else (ldx, K, M, N)
-    rc = getattr(lib, fn)(gy.data_ptr(), x.data_ptr(), *rows_args, ws.data_ptr(), nbytes, gw.data_ptr(),
-                          gb.data_ptr() if gb is not None else None, int(into is not None),
-                          torch.cuda.current_stream(gy.device).cuda_stream)
-    if rc == -1 and may_refuse:
-        return None
-    if rc != 0:
-        raise RuntimeError(f"{fn} failed (rc={rc})")
-    return gw, gb
+    rc = _call(fn, gy.data_ptr(), x.data_ptr(), *rows_args, ws.data_ptr(), nbytes, gw.data_ptr(),
+               gb.data_ptr() if gb is not None else None, int(into is not None), _stream(gy),
+               refusals=(-1,) if may_refuse else ())
+    return (gw, gb) if rc == 0 else None
 
 
 # the update's bf16 weight copies made by one multi-tensor cast per minibatch (param_shadows) instead of one cast
-# kernel per Linear weight and bias (T1_PARAM_SHADOWS=0: the per-layer casts, A/B)
-PARAM_SHADOWS = os.environ.get("T1_PARAM_SHADOWS", "1") != "0"
+# kernel per Linear weight and bias
 _ACTIVE_SHADOWS = {}
 
 
@@ -317,7 +295,7 @@ class _LinearSplitK(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda")
     def forward(ctx, x, w, b):
-        # the leaf parameters, for the backward's direct accumulation into their .grad (GRAD_DIRECT)
+        # the leaf parameters, for the backward's direct accumulation into their .grad (_grad_into)
         ctx.leaves = (w if w.is_leaf else None, b if b.is_leaf else None)
         if x.is_cuda and torch.is_autocast_enabled("cuda"):
             # the operands cast once, here, and saved cast: the backward's input-gradient GEMM and weight gradient use
@@ -326,7 +304,7 @@ class _LinearSplitK(torch.autograd.Function):
             dt = torch.get_autocast_dtype("cuda")
             x, w, b = x.to(dt), _cast_param(w, dt), _cast_param(b, dt)
         ctx.save_for_backward(x, w)
-        if (GEMM_F32 and x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and x.dim() == 2
+        if (x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and x.dim() == 2
                 and not torch.is_autocast_enabled("cuda")):
             return gemm_nt_f32(x, w, b)   # the fp32 update: the three-part-split HIP GEMM
         return torch.addmm(b, x, w.t())
@@ -336,34 +314,31 @@ class _LinearSplitK(torch.autograd.Function):
     def backward(ctx, gy):
         x, w = ctx.saved_tensors
         gy = gy.contiguous()
+        need_x, need_w, need_b = ctx.needs_input_grad
         gx = None
-        if ctx.needs_input_grad[0]:
-            if GEMM_F32 and gy.is_cuda and gy.dtype == torch.float32 and w.dtype == torch.float32:
+        if need_x:
+            if gy.is_cuda and gy.dtype == torch.float32 and w.dtype == torch.float32:
                 gx = gemm_nt_f32(gy, w.t())   # gy W as gy (W^T)^T: the reduction index contiguous in both operands
             else:
                 gx = gy.mm(w)
+        # on the device, by dtype, the HIP wgrad kernel: the bf16 update's, or the fp32 update's (the reference's
+        # precision); the split-K batched GEMM on the host and for other dtypes
         kern = None
-        if gy.is_cuda and ctx.needs_input_grad[1]:
-            if LINEAR_WGRAD and gy.dtype == torch.bfloat16:
+        if gy.is_cuda and need_w:
+            if gy.dtype == torch.bfloat16:
                 kern = linear_wgrad_bf16
-            elif LINEAR_WGRAD_F32 and gy.dtype == torch.float32 and x.dtype == torch.float32:
-                kern = linear_wgrad_f32   # the fp32 update (the reference's precision)
-        if kern is not None:
-            wl, bl = ctx.leaves
-            need_b = ctx.needs_input_grad[2]
-            if (GRAD_DIRECT and _DIRECT_GRAD[0] and wl is not None and wl.grad is not None and wl.grad.dtype == torch.float32
-                    and wl.grad.is_contiguous() and (not need_b or (bl is not None and bl.grad is not None
-                                                                    and bl.grad.dtype == torch.float32))):
-                # the weight / bias gradients added straight into the existing .grad (the PPO update's views into
-                # the all-reduce bucket) by the kernel's reduction: autograd's accumulation pass per parameter
-                # (one add_ kernel each, ~38 per minibatch) is not needed, so no gradient is returned for them
-                kern(gy, x, into=(wl.grad, bl.grad if need_b else None))
-                return gx, None, None
-            gw, gb = kern(gy, x, need_bias=need_b)
-            return gx, gw, gb
-        gw = wgrad_splitk(gy, x) if ctx.needs_input_grad[1] else None
-        gb = bias_grad(gy) if ctx.needs_input_grad[2] else None
-        return gx, gw, gb
+            elif gy.dtype == torch.float32 and x.dtype == torch.float32:
+                kern = linear_wgrad_f32
+        if kern is None:
+            return gx, wgrad_splitk(gy, x) if need_w else None, gy.sum(0) if need_b else None
+        into = _grad_into(*ctx.leaves, need_b)
+        if into is None:
+            return (gx, *kern(gy, x, need_bias=need_b))
+        # the weight / bias gradients added straight into the existing .grad by the kernel's reduction: autograd's
+        # accumulation pass per parameter (one add_ kernel each, ~38 per minibatch) is not needed, so no gradient is
+        # returned for them
+        kern(gy, x, into=into)
+        return gx, None, None
 
 
 def linear(x, layer):
@@ -394,13 +369,10 @@ def plain_copy(module):
     return copy.deepcopy(module)
 
 
-# the fp32 update's MLPs (actor, critic, state estimator) as one autograd node on the fused HIP GEMMs (_MlpF32; default,
-# T1_MLP_F32=0 runs them layer by layer): the ELU and ELU-backward passes (3.3 ms per update) go into the GEMM epilogues
-# -- update 38.1-38.2 -> 34.5-35.6 ms (profiles/r06t_*), once the epilogue loads its ELU outputs together (its first
-# form loaded them one by one behind the bounds checks and cost as much as it saved)
-MLP_F32 = os.environ.get("T1_MLP_F32", "1") == "1"
-
-
+# the fp32 update's MLPs (actor, critic, state estimator) as one autograd node on the fused HIP GEMMs (_MlpF32): the
+# ELU and ELU-backward passes (3.3 ms per update) go into the GEMM epilogues -- update 38.1-38.2 -> 34.5-35.6 ms
+# (profiles/r06t_*), once the epilogue loads its ELU outputs together (its first form loaded them one by one behind
+# the bounds checks and cost as much as it saved)
 class _MlpF32(torch.autograd.Function):
     """Linear, ELU, Linear, ELU, ..., Linear (actor_critic_dh.py:45-111) in the fp32 update on the matrix cores, with
     each ELU fused into a GEMM: forward, every hidden layer is gemm_nt_f32(x, W, b, ELU) (no separate ELU pass over
@@ -431,21 +403,17 @@ class _MlpF32(torch.autograd.Function):
         x, params, outs = saved[0], saved[1:1 + 2 * n], saved[1 + 2 * n:]
         grads = [None] * (2 * n)
         g = g.contiguous()
-        direct = GRAD_DIRECT and _DIRECT_GRAD[0]
         gx = None
         for i in range(n - 1, -1, -1):
             w = params[2 * i]
             inp = x if i == 0 else outs[i - 1]
             need_w, need_b = ctx.needs_input_grad[1 + 2 * i], ctx.needs_input_grad[2 + 2 * i]
-            wl, bl = ctx.leaves[2 * i], ctx.leaves[2 * i + 1]
             if need_w:
-                if (direct and wl is not None and wl.grad is not None and wl.grad.dtype == torch.float32
-                        and wl.grad.is_contiguous() and (not need_b or (bl is not None and bl.grad is not None
-                                                                        and bl.grad.dtype == torch.float32))):
-                    linear_wgrad_f32(g, inp, into=(wl.grad, bl.grad if need_b else None))
+                into = _grad_into(ctx.leaves[2 * i], ctx.leaves[2 * i + 1], need_b)
+                if into is not None:
+                    linear_wgrad_f32(g, inp, into=into)
                 else:
-                    grads[2 * i], gb = linear_wgrad_f32(g, inp, need_bias=need_b)
-                    grads[2 * i + 1] = gb
+                    grads[2 * i], grads[2 * i + 1] = linear_wgrad_f32(g, inp, need_bias=need_b)
             elif need_b:
                 grads[2 * i + 1] = g.sum(0)
             if i > 0:
@@ -472,8 +440,8 @@ class MLP(nn.Sequential):
         return True
 
     def forward(self, x):
-        if (MLP_F32 and GEMM_F32 and LINEAR_WGRAD_F32 and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
-                and torch.is_grad_enabled() and not torch.is_autocast_enabled("cuda") and self._fusable()):
+        if (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and torch.is_grad_enabled()
+                and not torch.is_autocast_enabled("cuda") and self._fusable()):
             params = []
             for m in list(self)[::2]:
                 params += [m.weight, m.bias]
@@ -497,8 +465,6 @@ def conv1d_direct(x, conv):
     a shape the library has no instance of (the caller keeps the GEMM path).  An fp16 x (the env's fp16 histories) is
     read as it is by the packed kernel's fp16 instance (t1policy_conv1d_forward_packed_h, y fp32 all the same); None
     too for an fp16 x the kernel cannot take (a base off a 4-byte boundary, 2 GiB or more)."""
-    from .. import _lib
-    lib = _lib.load()
     k, st = conv.kernel_size[0], conv.stride[0]
     x = x.contiguous()
     B, C, L = x.shape
@@ -508,24 +474,17 @@ def conv1d_direct(x, conv):
         return None
     bias = conv.bias.detach().contiguous()
     y = torch.empty(B, lout, O, device=x.device, dtype=torch.float32)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    if x.dtype == torch.float16:
-        frag = packed_conv_weights(conv, stream)
-        rc = 1 if frag is None else lib.t1policy_conv1d_forward_packed_h(
-            x.data_ptr(), frag.data_ptr(), bias.data_ptr(), y.data_ptr(), B, C, L, O, k, st, stream)
-    elif x.data_ptr() % 16 == 0 and B * C * L * 4 < 2 ** 31:
-        frag = packed_conv_weights(conv, stream)
-        rc = 1 if frag is None else lib.t1policy_conv1d_forward_packed(
-            x.data_ptr(), frag.data_ptr(), bias.data_ptr(), y.data_ptr(), B, C, L, O, k, st, stream)
+    stream = _stream(x)
+    if x.dtype == torch.float16 or (x.data_ptr() % 16 == 0 and B * C * L * 4 < 2 ** 31):
+        fn = "t1policy_conv1d_forward_packed_h" if x.dtype == torch.float16 else "t1policy_conv1d_forward_packed"
+        w = packed_conv_weights(conv, stream)
+        if w is None:
+            return None
     else:
-        wt = conv.weight.detach().permute(1, 2, 0).contiguous()   # tap-major: wt[c, t, o]
-        rc = lib.t1policy_conv1d_forward(x.data_ptr(), wt.data_ptr(), bias.data_ptr(), y.data_ptr(), B, C, L, O, k,
-                                         st, stream)
-    if rc == 1:
-        return None
-    if rc != 0:
-        raise RuntimeError(f"t1policy_conv1d_forward failed (rc={rc})")
-    return y
+        fn = "t1policy_conv1d_forward"
+        w = conv.weight.detach().permute(1, 2, 0).contiguous()   # tap-major: wt[c, t, o]
+    rc = _call(fn, x.data_ptr(), w.data_ptr(), bias.data_ptr(), y.data_ptr(), B, C, L, O, k, st, stream, refusals=(1,))
+    return y if rc == 0 else None
 
 
 def packed_conv_weights(conv, stream=None, force=False):
@@ -534,24 +493,19 @@ def packed_conv_weights(conv, stream=None, force=False):
     step) moves the weight's version counter; a REPLAYED optimizer step (the graphed PPO update) does not -- a graph
     replay bypasses the dispatcher -- so DHPPO.update() repacks with force=True after every update.  A
     captured act() graph reads the buffer in place.  None for a shape the library has no instance of."""
-    from .. import _lib
     w = conv.weight
     key = (w._version, w.data_ptr())
     frag = getattr(conv, "_t1_frag", None)
     if not force and frag is not None and getattr(conv, "_t1_frag_key", None) == key:
         return frag
-    lib = _lib.load()
     if frag is None or frag.device != w.device:
-        frag = torch.empty(lib.t1policy_conv1d_frag_bytes(), device=w.device, dtype=torch.uint8)
+        frag = torch.empty(_load().t1policy_conv1d_frag_bytes(), device=w.device, dtype=torch.uint8)
     if stream is None:
-        stream = torch.cuda.current_stream(w.device).cuda_stream
+        stream = _stream(w)
     wc = w.detach().contiguous()
-    rc = lib.t1policy_conv1d_pack_weights(wc.data_ptr(), frag.data_ptr(), conv.in_channels, conv.out_channels,
-                                          conv.kernel_size[0], stream)
-    if rc == 1:
+    if _call("t1policy_conv1d_pack_weights", wc.data_ptr(), frag.data_ptr(), conv.in_channels, conv.out_channels,
+             conv.kernel_size[0], stream, refusals=(1,)):
         return None
-    if rc != 0:
-        raise RuntimeError(f"t1policy_conv1d_pack_weights failed (rc={rc})")
     conv._t1_frag, conv._t1_frag_key = frag, key
     return frag
 
@@ -590,7 +544,6 @@ def packed_heads_weights(ac, stream=None, force=False):
     counter, a graph-replayed optimizer step does not, so DHPPO.update() repacks with force=True after every update and
     DHPPO._graphed_act refreshes before each replay.  The pack ran on every act() before (5 us of 0.14 ms, VERDICT r5
     #4).  Returns (frag, ptrs, dims), or None when the model has no compiled instance."""
-    from .. import _lib
     layers = _heads_layers(ac)
     if layers is None:
         return None
@@ -602,127 +555,84 @@ def packed_heads_weights(ac, stream=None, force=False):
     frag = getattr(ac, "_t1_heads_frag", None)
     if not force and frag is not None and frag.device == dev and getattr(ac, "_t1_heads_key", None) == key:
         return frag, ptrs_c, dims_c
-    lib = _lib.load()
     if frag is None or frag.device != dev:
-        frag = torch.empty(lib.t1policy_heads_frag_bytes(), device=dev, dtype=torch.uint8)
+        frag = torch.empty(_load().t1policy_heads_frag_bytes(), device=dev, dtype=torch.uint8)
     if stream is None:
         stream = torch.cuda.current_stream(dev).cuda_stream
-    rc = lib.t1policy_heads_pack(ptrs_c, dims_c, frag.data_ptr(), stream)
-    if rc == 1:
+    if _call("t1policy_heads_pack", ptrs_c, dims_c, frag.data_ptr(), stream, refusals=(1,)):
         return None
-    if rc != 0:
-        raise RuntimeError(f"t1policy_heads_pack failed (rc={rc})")
     ac._t1_heads_frag, ac._t1_heads_key = frag, key
     return frag, ptrs_c, dims_c
 
 
-# the update's first history conv as HIP kernels under the bf16 update (T1_CONV1_TRAIN=0: unfold + GEMM, A/B)
-CONV1_TRAIN = os.environ.get("T1_CONV1_TRAIN", "1") != "0"
+# the first history conv's HIP entries per operand dtype (the dtype of x and of the output): weight pack, its fragment
+# bytes, forward, weight gradient.
+#   bf16 (the opt-in bf16 update): t1policy_conv1_forward_bf16 has autocast's addmm arithmetic, t1policy_conv1_wgrad_bf16
+#        fp32 sums in a fixed order;
+#   fp32 (the reference's precision, dh_ppo.py:155-182): the forward is the fp32-accurate packed direct conv
+#        (t1policy_conv1d_forward_packed: split fp16 operands, the rollout's inference kernel), the weight gradient
+#        t1policy_conv1_wgrad_f32 (three-part bf16 split, six MFMAs: fp32-class, fixed-order sums).
+_CONV1_ENTRIES = {
+    torch.bfloat16: ("t1policy_conv1_pack_bf16", "t1policy_conv1_bf16_frag_bytes", "t1policy_conv1_forward_bf16",
+                     "t1policy_conv1_wgrad_bf16"),
+    torch.float32: ("t1policy_conv1d_pack_weights", "t1policy_conv1d_frag_bytes", "t1policy_conv1d_forward_packed",
+                    "t1policy_conv1_wgrad_f32"),
+}
 
 
-def _conv1_train_call(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed (rc={rc})")
-
-
-class _HistoryConvBf16(torch.autograd.Function):
-    """The history encoder's first Conv1d in the PPO update on bf16 inputs (the opt-in bf16 update): the HIP forward
-    (t1policy_conv1_forward_bf16, channels-last (B, Lout, O) bf16, autocast's addmm arithmetic) and weight gradient
-    (t1policy_conv1_wgrad_bf16: fp32 sums in a fixed order), no unfolded copy of the input.  The input is the
-    observation history, which needs no gradient."""
+class _HistoryConv(torch.autograd.Function):
+    """The history encoder's first Conv1d in the PPO update on a bf16 or fp32 input as HIP kernels (_CONV1_ENTRIES):
+    channels-last (B, 14, 32) out in x's dtype, as conv1d_as_gemm -- no unfolded (B x 14, 396) copy of the input (667 us
+    per minibatch in fp32) and no split-K GEMM on it.  The weights are packed on every call (inside a captured update
+    graph the optimizer's replayed steps move no version counter).  The input is the observation history, which
+    needs no gradient."""
 
     @staticmethod
     def forward(ctx, x, weight, bias):
-        from .. import _lib
-        lib = _lib.load()
+        pack, frag_bytes, fwd, _ = _CONV1_ENTRIES[x.dtype]
         B, C, L = x.shape
         O, _, K = weight.shape
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        frag = torch.empty(lib.t1policy_conv1_bf16_frag_bytes(), device=x.device, dtype=torch.uint8)
-        _conv1_train_call(lib.t1policy_conv1_pack_bf16(weight.detach().contiguous().data_ptr(), frag.data_ptr(), C, O, K,
-                                                       stream), "t1policy_conv1_pack_bf16")
-        lout = (L - K) // 3 + 1
-        y = torch.empty(B, lout, O, device=x.device, dtype=torch.bfloat16)
-        _conv1_train_call(lib.t1policy_conv1_forward_bf16(x.data_ptr(), frag.data_ptr(),
-                                                          bias.detach().contiguous().data_ptr(), y.data_ptr(), B, C, L,
-                                                          O, K, 3, stream), "t1policy_conv1_forward_bf16")
+        stream = _stream(x)
+        frag = torch.empty(getattr(_load(), frag_bytes)(), device=x.device, dtype=torch.uint8)
+        _call(pack, weight.detach().contiguous().data_ptr(), frag.data_ptr(), C, O, K, stream)
+        y = torch.empty(B, (L - K) // 3 + 1, O, device=x.device, dtype=x.dtype)
+        _call(fwd, x.data_ptr(), frag.data_ptr(), bias.detach().contiguous().data_ptr(), y.data_ptr(), B, C, L, O, K, 3,
+              stream)
         ctx.save_for_backward(x)
         ctx.shape = (C, L, O, K)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        from .. import _lib
-        lib = _lib.load()
         x, = ctx.saved_tensors
         C, L, O, K = ctx.shape
-        gy = gy.to(torch.bfloat16).contiguous()
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        ws = torch.empty(lib.t1policy_conv1_bf16_workspace_bytes(), device=x.device, dtype=torch.uint8)
+        gy = gy.to(x.dtype).contiguous()
+        ws = torch.empty(_load().t1policy_conv1_bf16_workspace_bytes(), device=x.device, dtype=torch.uint8)
         gw = torch.empty(O, C, K, device=x.device, dtype=torch.float32)
         gb = torch.empty(O, device=x.device, dtype=torch.float32)
-        _conv1_train_call(lib.t1policy_conv1_wgrad_bf16(x.data_ptr(), gy.data_ptr(), ws.data_ptr(), gw.data_ptr(),
-                                                        gb.data_ptr(), x.shape[0], C, L, O, K, 3, stream),
-                          "t1policy_conv1_wgrad_bf16")
+        _call(_CONV1_ENTRIES[x.dtype][3], x.data_ptr(), gy.data_ptr(), ws.data_ptr(), gw.data_ptr(), gb.data_ptr(),
+              x.shape[0], C, L, O, K, 3, _stream(x))
         return None, gw, gb
 
 
-class _HistoryConvF32(torch.autograd.Function):
-    """The history encoder's first Conv1d in the fp32 PPO update (the reference's precision, dh_ppo.py:155-182): the
-    forward as the fp32-accurate packed direct conv (t1policy_conv1d_forward_packed: split fp16 operands, the rollout's
-    inference kernel), the weights packed on every call (inside a captured update graph the optimizer's replayed steps
-    move no version counter), and the weight gradient as t1policy_conv1_wgrad_f32 (three-part bf16 split, six MFMAs:
-    fp32-class, fixed-order sums) -- no unfolded (B x 14, 396) copy (667 us per minibatch) and no split-K GEMM on it.
-    Channels-last (B, 14, 32) fp32 out, as conv1d_as_gemm.  The input is the observation history (no gradient)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
-        from .. import _lib
-        lib = _lib.load()
-        B, C, L = x.shape
-        O, _, K = weight.shape
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        frag = torch.empty(lib.t1policy_conv1d_frag_bytes(), device=x.device, dtype=torch.uint8)
-        _conv1_train_call(lib.t1policy_conv1d_pack_weights(weight.detach().contiguous().data_ptr(), frag.data_ptr(), C,
-                                                           O, K, stream), "t1policy_conv1d_pack_weights")
-        lout = (L - K) // 3 + 1
-        y = torch.empty(B, lout, O, device=x.device, dtype=torch.float32)
-        _conv1_train_call(lib.t1policy_conv1d_forward_packed(x.data_ptr(), frag.data_ptr(),
-                                                             bias.detach().contiguous().data_ptr(), y.data_ptr(), B, C,
-                                                             L, O, K, 3, stream), "t1policy_conv1d_forward_packed")
-        ctx.save_for_backward(x)
-        ctx.shape = (C, L, O, K)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        from .. import _lib
-        lib = _lib.load()
-        x, = ctx.saved_tensors
-        C, L, O, K = ctx.shape
-        gy = gy.float().contiguous()
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        ws = torch.empty(lib.t1policy_conv1_bf16_workspace_bytes(), device=x.device, dtype=torch.uint8)
-        gw = torch.empty(O, C, K, device=x.device, dtype=torch.float32)
-        gb = torch.empty(O, device=x.device, dtype=torch.float32)
-        _conv1_train_call(lib.t1policy_conv1_wgrad_f32(x.data_ptr(), gy.data_ptr(), ws.data_ptr(), gw.data_ptr(),
-                                                       gb.data_ptr(), x.shape[0], C, L, O, K, 3, stream),
-                          "t1policy_conv1_wgrad_f32")
-        return None, gw, gb
+def _is_first_history_conv(x, conv):
+    """conv is the encoder's first Conv1d (66 -> 32 channels, kernel 6, stride 3, with a bias) and x its (B, 66, 47)
+    input: the one shape the HIP training kernels have."""
+    return ((conv.in_channels, conv.out_channels, conv.kernel_size[0], conv.stride[0]) == (66, 32, 6, 3)
+            and x.dim() == 3 and x.shape[1:] == (66, 47) and conv.padding == (0,) and conv.dilation == (1,)
+            and conv.groups == 1 and conv.bias is not None)
 
 
 def conv1d_train_f32(x, conv):
     """The first history conv of the fp32 update on an fp32 (B, 66, 47) input as the HIP kernels (channels-last (B, 14,
     32) fp32 out), or None when the conv or the input is not that shape (the caller keeps unfold + GEMM)."""
-    if (conv.in_channels, conv.out_channels, conv.kernel_size[0], conv.stride[0]) != (66, 32, 6, 3) or \
-            x.dim() != 3 or x.shape[1:] != (66, 47) or x.dtype != torch.float32 or conv.padding != (0,) or \
-            conv.dilation != (1,) or conv.groups != 1 or conv.bias is None or conv.weight.dtype != torch.float32 or \
+    if not _is_first_history_conv(x, conv) or x.dtype != torch.float32 or conv.weight.dtype != torch.float32 or \
             torch.is_autocast_enabled("cuda"):
         return None
     x = x.contiguous()
     if x.data_ptr() % 16 != 0 or x.numel() * 4 >= 2 ** 31:
         return None
-    return _HistoryConvF32.apply(x, conv.weight, conv.bias)
+    return _HistoryConv.apply(x, conv.weight, conv.bias)
 
 
 def _bf16_operands(x):
@@ -736,14 +646,12 @@ def _bf16_operands(x):
 def conv1d_train_bf16(x, conv):
     """The first history conv of the update on a bf16 (B, 66, 47) input as the HIP kernels (channels-last (B, 14, 32)
     bf16 out), or None when the conv or the input is not that shape (the caller keeps unfold + GEMM)."""
-    if (conv.in_channels, conv.out_channels, conv.kernel_size[0], conv.stride[0]) != (66, 32, 6, 3) or \
-            x.dim() != 3 or x.shape[1:] != (66, 47) or x.dtype != torch.bfloat16 or conv.padding != (0,) or \
-            conv.dilation != (1,) or conv.groups != 1 or conv.bias is None:
+    if not _is_first_history_conv(x, conv) or x.dtype != torch.bfloat16:
         return None
     x = x.contiguous()
     if x.data_ptr() % 4 != 0:
         return None
-    return _HistoryConvBf16.apply(x, conv.weight, conv.bias)
+    return _HistoryConv.apply(x, conv.weight, conv.bias)
 
 
 def _heads_layers(ac):
@@ -770,7 +678,6 @@ def heads_forward(ac, obs, critic_obs, eps):
     results of the fp32 kernels on the widened inputs); mixed dtypes return None.  The weights are packed
     into the kernel's split fp16 fragments when a parameter changed (packed_heads_weights); a captured act() graph
     reads them in place and is refreshed before each replay."""
-    from .. import _lib
     layers = _heads_layers(ac)
     if (layers is None or not obs.is_cuda or obs.dtype not in (torch.float32, torch.float16)
             or critic_obs.dtype != obs.dtype or obs.dim() != 2 or critic_obs.dim() != 2 or eps.shape != (obs.shape[0], ac.std.numel())):
@@ -780,7 +687,6 @@ def heads_forward(ac, obs, critic_obs, eps):
     if (critic_obs.shape[0] != obs.shape[0] or obs.shape[1] != ac.in_channels * ac.num_proprio_obs
             or critic_obs.shape[1] != layers[11].in_features):
         return None
-    lib = _lib.load()
     if _heads_args(ac, layers) is None or ac.std.device != obs.device:
         return None
     dev = obs.device
@@ -800,20 +706,11 @@ def heads_forward(ac, obs, critic_obs, eps):
     actions, sigma = torch.empty_like(mean), torch.empty_like(mean)
     logp = torch.empty(B, device=dev)
     value = torch.empty(B, 1, device=dev)
-    entry = lib.t1policy_heads_forward_h if obs.dtype == torch.float16 else lib.t1policy_heads_forward
-    rc = entry(ptrs_c, dims_c, frag.data_ptr(), y1.data_ptr(), obs.data_ptr(), obs.shape[1], critic_obs.data_ptr(),
-               critic_obs.shape[1], eps.data_ptr(), mean.data_ptr(), actions.data_ptr(), sigma.data_ptr(),
-               logp.data_ptr(), value.data_ptr(), B, stream)
-    if rc == 1:
-        return None
-    if rc != 0:
-        raise RuntimeError(f"t1policy_heads_forward failed (rc={rc})")
-    return mean, actions, sigma, logp, value
-
-
-# the unfolded rows' input gradient as the HIP gather (t1policy_fold_rows) instead of torch's unfold backward
-# (T1_FOLD_ROWS=0: torch's, A/B)
-FOLD_ROWS = os.environ.get("T1_FOLD_ROWS", "1") != "0"
+    entry = "t1policy_heads_forward_h" if obs.dtype == torch.float16 else "t1policy_heads_forward"
+    rc = _call(entry, ptrs_c, dims_c, frag.data_ptr(), y1.data_ptr(), obs.data_ptr(), obs.shape[1],
+               critic_obs.data_ptr(), critic_obs.shape[1], eps.data_ptr(), mean.data_ptr(), actions.data_ptr(),
+               sigma.data_ptr(), logp.data_ptr(), value.data_ptr(), B, stream, refusals=(1,))
+    return (mean, actions, sigma, logp, value) if rc == 0 else None
 
 
 class _UnfoldRows(torch.autograd.Function):
@@ -830,15 +727,10 @@ class _UnfoldRows(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from .. import _lib
-        lib = _lib.load()
         (B, L, C), k, st = ctx.geom
         g = g.contiguous()
         gx = torch.empty(B, L, C, device=g.device, dtype=g.dtype)
-        rc = lib.t1policy_fold_rows(g.data_ptr(), gx.data_ptr(), B, L, C, k, st, g.element_size(),
-                                    torch.cuda.current_stream(g.device).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f"t1policy_fold_rows failed (rc={rc})")
+        _call("t1policy_fold_rows", g.data_ptr(), gx.data_ptr(), B, L, C, k, st, g.element_size(), _stream(g))
         return gx, None, None
 
 
@@ -846,25 +738,23 @@ def conv1d_as_gemm(x, conv, channels_last=False):
     """nn.Conv1d (no padding / dilation / groups) as one GEMM over unfolded windows.  x: (B, C, L), or (B, L, C) with
     channels_last; returns (B, Lout, O) (channels last).  The windows x[b, :, s*l : s*l + k] become rows of a
     (B*Lout, C*k) matrix (c-major, then tap: the layout of conv.weight.view(O, C*k)), so the product is one
-    hipBLASLt GEMM + bias, and autograd's unfold backward (a strided scatter-add) gives the input gradient."""
+    hipBLASLt GEMM + bias.  The input gradient of a channels-last device x is the HIP gather (_UnfoldRows), otherwise
+    autograd's unfold backward (a strided scatter-add)."""
     k, st = conv.kernel_size[0], conv.stride[0]
-    if (channels_last and FOLD_ROWS and x.is_cuda and torch.is_grad_enabled() and x.requires_grad
+    if (channels_last and x.is_cuda and torch.is_grad_enabled() and x.requires_grad
             and x.dtype in (torch.bfloat16, torch.float32)):
-        rows = _UnfoldRows.apply(x, k, st)               # (B * Lout, C * k), the HIP gather as its backward
-        B, Lout = x.shape[0], (x.shape[1] - k) // st + 1
-        return _LinearSplitK.apply(rows, conv.weight.reshape(conv.out_channels, -1), conv.bias).view(B, Lout, -1)
-    if channels_last:
-        win = x.unfold(1, k, st)                      # (B, Lout, C, k)
+        rows = _UnfoldRows.apply(x, k, st)
     else:
-        win = x.unfold(2, k, st).permute(0, 2, 1, 3)  # (B, C, Lout, k) -> (B, Lout, C, k)
-    B, Lout, C, _ = win.shape
-    rows = win.reshape(B * Lout, C * k)
-    w = conv.weight.reshape(conv.out_channels, C * k)
+        # (B, Lout, C, k); from (B, C, L) by way of (B, C, Lout, k)
+        win = x.unfold(1, k, st) if channels_last else x.unfold(2, k, st).permute(0, 2, 1, 3)
+        rows = win.reshape(win.shape[0] * win.shape[1], win.shape[2] * k)
+    w = conv.weight.reshape(conv.out_channels, rows.shape[1])
     if torch.is_grad_enabled():   # split-K weight gradient (K = B * Lout rows)
         y = _LinearSplitK.apply(rows, w, conv.bias)
     else:
         y = torch.addmm(conv.bias, rows, w.t())
-    return y.view(B, Lout, conv.out_channels)
+    lout = (x.shape[1 if channels_last else 2] - k) // st + 1
+    return y.view(x.shape[0], lout, conv.out_channels)
 
 
 class HistoryEncoder(nn.Sequential):
@@ -884,10 +774,10 @@ class HistoryEncoder(nn.Sequential):
                 y = None
                 if not last and not torch.is_grad_enabled() and x.dtype == torch.float32 and m.weight.dtype == x.dtype:
                     y = conv1d_direct(x, m)   # inference (the rollout's act()): the HIP direct conv
-                elif not last and torch.is_grad_enabled() and CONV1_TRAIN and _bf16_operands(x):
+                elif not last and torch.is_grad_enabled() and _bf16_operands(x):
                     # the bf16 update: the HIP forward + weight gradient on the bf16 operands autocast would make
                     y = conv1d_train_bf16(x.to(torch.bfloat16), m)
-                elif not last and torch.is_grad_enabled() and CONV1_TRAIN and x.dtype == torch.float32:
+                elif not last and torch.is_grad_enabled() and x.dtype == torch.float32:
                     # the fp32 update: the fp32-accurate HIP forward + three-part-split weight gradient
                     y = conv1d_train_f32(x, m)
                 x = y if y is not None else conv1d_as_gemm(x, m, channels_last=last)

@@ -31,10 +31,8 @@ from . import distributed as dist_util
 from .dh_policy import ActorCriticDH, heads_forward, refresh_packed_weights
 from .rollout import RolloutStorage
 
-# the update's gradient clipping over the flat gradient bucket on the device (T1_FLAT_CLIP=0: torch's
-# clip_grad_norm_, A/B)
-FLAT_CLIP = os.environ.get("T1_FLAT_CLIP", "1") != "0"
-# the rollout's act() through the fused HIP heads (t1policy_heads_forward; T1_FUSED_ACT=0: the torch layers, A/B)
+# the rollout's act() through the fused HIP heads (t1policy_heads_forward; T1_FUSED_ACT=0: the torch layers -- the
+# one opt-out, tools/act_bench.py --torch)
 FUSED_ACT = os.environ.get("T1_FUSED_ACT", "1") != "0"
 
 
@@ -388,7 +386,7 @@ class DHPPO:
         (one reduction and one scale instead of torch's per-tensor norms, a norm of the norms and a scale per tensor:
         ~110 us per minibatch); the same clip, the squares summed in another order (fp32).  On the host torch's."""
         g = self.grads
-        if FLAT_CLIP and g.flat.is_cuda:
+        if g.flat.is_cuda:
             g.bind_()   # every .grad is its bucket view (no-op unless something replaced one)
             coef = torch.clamp(self.max_grad_norm / (torch.linalg.vector_norm(g.flat) + 1e-6), max=1.0)
             g.flat.mul_(coef)
@@ -577,7 +575,7 @@ class DHPPO:
         """The reference's minibatch losses (dh_ppo.py:130-178); the distribution terms in fp32 under autocast.  Under
         the device autocast the parameters' low-precision copies are made by one multi-tensor cast first
         (dh_policy.param_shadows: the same values as the per-layer casts)."""
-        if args[0].is_cuda and torch.is_autocast_enabled("cuda") and dh_policy.PARAM_SHADOWS:
+        if args[0].is_cuda and torch.is_autocast_enabled("cuda"):
             with dh_policy.param_shadows(ac, torch.get_autocast_dtype("cuda")):
                 return self._losses_body(ac, *args)
         return self._losses_body(ac, *args)

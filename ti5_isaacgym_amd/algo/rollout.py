@@ -12,8 +12,6 @@ when an env resets (t1_dh_stand_env.py:368-481, 548-558).  Storing all 24 x 8192
 newest frame (137 MB in all), and the minibatch generator rebuilds every sampled history from them and the stored
 dones -- the same bits as the full rows.  Callers whose observations are not such a history keep the full storage.
 """
-import os
-
 import warnings
 
 import torch
@@ -21,13 +19,9 @@ import torch
 from . import distributed as dist_util
 
 
-# the minibatch's per-transition fields gathered by one HIP launch on the device (t1policy_gather_rows; T1_GATHER_ROWS=0:
-# torch's index per field, A/B)
-GATHER_ROWS = os.environ.get("T1_GATHER_ROWS", "1") != "0"
-
-
 class _FieldGather:
-    """fields[k][idx] for every field by one launch (t1policy_gather_rows): 2-D, contiguous, 32-bit device tensors of
+    """The minibatch's per-transition fields, fields[k][idx] for every field, by one launch on the device
+    (t1policy_gather_rows) instead of torch's index per field: 2-D, contiguous, 32-bit device tensors of
     the same row count; anything else is indexed by torch.  Output buffers are fresh per call (graph-pool memory
     inside a captured update)."""
 
@@ -211,7 +205,7 @@ class RolloutStorage:
         if self.next_proprio_obs is not None:
             extra = (flat(self.next_proprio_obs), flat(self.rewards))
 
-        gather = _FieldGather([critic] + cols) if (GATHER_ROWS and critic is not obs) else None
+        gather = _FieldGather([critic] + cols) if critic is not obs else None
 
         def take(idx):
             if gather is not None and idx.is_cuda:

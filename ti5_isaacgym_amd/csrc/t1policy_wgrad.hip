@@ -3,7 +3,7 @@
 // fixed-order reduction -- what loss.backward() computes for every nn.Linear of the policy (dh_ppo.py:180,
 // actor_critic_dh.py:45-111), at the update's 49,152-row minibatch.
 //
-// The build's path before this (dh_policy.wgrad_splitk + bias_grad): a hipBLASLt strided-batched GEMM over 24 slices
+// The build's path before this (dh_policy.wgrad_splitk + gy.sum(0)): a hipBLASLt strided-batched GEMM over 24 slices
 // of 2,048 rows, the slices summed by t1policy_slice_sum, and torch's dim-0 sum for the bias -- three launches per
 // layer and 10 ms of device time per update (bmm 5.4 ms + sums 4.7 ms, profiles/r04q_ppo_update_profile_bf16_eager.txt)
 // for ~0.7 TFLOP.
@@ -552,16 +552,8 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(const float* __restrict__ 
   }
 }
 
-// workgroups per CU the slicing aims at (T1_WGRAD_WG_PER_CU, 1-4: A/B; fewer means fewer, longer slices and
-// less partial traffic)
-int wg_per_cu() {
-  static const int v = [] {
-    const char* e = getenv("T1_WGRAD_WG_PER_CU");
-    const int k = e ? atoi(e) : 2;
-    return k >= 1 && k <= 4 ? k : 2;
-  }();
-  return v;
-}
+// workgroups per CU the slicing aims at (fewer means fewer, longer slices and less partial traffic)
+constexpr int WG_PER_CU = 2;
 
 // T1_WGRAD_STAGED (A/B): 1 (default) k_linear_wgrad_f32s, 0 the first fp32 form k_linear_wgrad_f32
 bool wgrad_staged() {
@@ -580,8 +572,8 @@ WgPlan wg_plan(int rows, int M, int N, int cus) {
   WgPlan p;
   p.tiles_m = (M + WG_T - 1) / WG_T;
   p.tiles = p.tiles_m * ((N + WG_T - 1) / WG_T);
-  // about wg_per_cu() workgroups per CU, slices of at least WG_MIN_ROWS rows, a multiple of the chunk
-  const int want = (wg_per_cu() * cus + p.tiles - 1) / p.tiles;
+  // about WG_PER_CU workgroups per CU, slices of at least WG_MIN_ROWS rows, a multiple of the chunk
+  const int want = (WG_PER_CU * cus + p.tiles - 1) / p.tiles;
   const int most = (rows + WG_MIN_ROWS - 1) / WG_MIN_ROWS;
   int sl = want < most ? want : most;
   if (sl < 1) sl = 1;

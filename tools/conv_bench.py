@@ -1,5 +1,5 @@
 """Time the policy history conv kernels (include/t1policy.h) at the rollout's batch: the tap-major k_conv1d_mfma
-(t1policy_conv1d_forward) against the packed-fragment k_conv1d_regs (t1policy_conv1d_pack_weights +
+(t1policy_conv1d_forward) against the packed-fragment k_conv1d_pair (t1policy_conv1d_pack_weights +
 t1policy_conv1d_forward_packed), HIP events around each launch on one stream, and each against torch's fp64 conv.
 
     python tools/conv_bench.py [--batch 8192] [--iters 200] [--out gpurun_out/conv.json]
@@ -76,14 +76,8 @@ for name, y in (("old", y_old), ("packed", y_new)):
     res[name + "_max_rel_err"] = err
 res["old"] = timed(old, a.iters)
 res["pack"] = timed(pack, a.iters)
-res["packed"] = timed(new, a.iters)   # k_conv1d_pair (default)
-os.environ["T1POLICY_CONV"] = "regs"
-new()
-torch.cuda.synchronize()
-res["packed_regs_max_rel_err"] = ((y_new.double() - ref).abs() / (1 + ref.abs())).max().item()
-res["packed_regs"] = timed(new, a.iters)
-del os.environ["T1POLICY_CONV"]
-for k in ("old", "packed", "packed_regs"):
+res["packed"] = timed(new, a.iters)   # k_conv1d_pair
+for k in ("old", "packed"):
     res[k]["GBs"] = (res["bytes_in"] + res["bytes_out"]) / (res[k]["median_us"] * 1e-6) / 1e9
 print(json.dumps(res))
 if a.out:
