@@ -80,6 +80,33 @@ int t1policy_heads_forward_h(const uint64_t* params, const int* dims, const void
                              const float* eps, float* mean, float* actions, float* sigma, float* logp,
                              float* value, int batch, void* stream);
 
+/* The deterministic policy and the critic's value as one-role launches of the same kernel (t1policy_heads.hip,
+ * k_heads64 with every workgroup of the grid one role; 32 envs per workgroup while every 32-env tile has a CU of its
+ * own, 64 above that, T1POLICY_INFER_TILE=32|64 overrides -- the two tilings give the same bits).
+ *
+ * actor_forward replaces ActorCriticDH.act_inference (actor_critic_dh.py:163-183: long_history, state_estimator and
+ * actor on the observations, no sample) after the first conv: the history tail, the state estimator and the actor.
+ *   mean    (batch, 12): bit-identical to t1policy_heads_forward's mean on the same frag / y1 / obs (the same layer
+ *           calls and k order per env column); no eps or std is read, no sample, sigma or log-prob written
+ *   est_vel (batch, 3): the state estimator's output (the estimated base linear velocity, the deployed policy's second
+ *           output), the fp32 value before it is split for the actor's first layer
+ * critic_forward replaces ActorCriticDH.evaluate (actor_critic_dh.py:185-188) for inference:
+ *   value   (batch): bit-identical to t1policy_heads_forward's value on the same frag / critic_obs
+ * Same params / dims / frag as t1policy_heads_forward (pack with t1policy_heads_pack); y1, obs, critic_obs as there.
+ * The _h entries read fp16 obs / critic_obs in place (any 2-byte alignment; an odd address returns -1) and equal the
+ * fp32 entries on the widened (finite) inputs bit for bit.  Every refusal is decided on the host before any launch:
+ * 0 on success (batch == 0 included), 1 for shapes without a compiled instance (dims, obs_cols < 235,
+ * critic_cols != 219), -1 on bad arguments (a null pointer, batch < 0, a frag off a 16-byte boundary, an odd fp16
+ * address), -2 on a launch error. */
+int t1policy_actor_forward(const uint64_t* params, const int* dims, const void* frag, const float* y1,
+                           const float* obs, int obs_cols, float* mean, float* est_vel, int batch, void* stream);
+int t1policy_actor_forward_h(const uint64_t* params, const int* dims, const void* frag, const float* y1,
+                             const void* obs, int obs_cols, float* mean, float* est_vel, int batch, void* stream);
+int t1policy_critic_forward(const uint64_t* params, const int* dims, const void* frag, const float* critic_obs,
+                            int critic_cols, float* value, int batch, void* stream);
+int t1policy_critic_forward_h(const uint64_t* params, const int* dims, const void* frag, const void* critic_obs,
+                              int critic_cols, float* value, int batch, void* stream);
+
 /* The same first conv in the PPO update under the opt-in bf16 update (t1policy_train.hip), forward and weight
  * gradient on bf16 inputs without the unfolded copy (the autograd path dh_policy.conv1d_as_gemm unfolds 545 MB per
  * minibatch).  Shapes as t1policy_conv1d_forward (only 66/47/32/6/3 compiled; 1 otherwise).

@@ -107,7 +107,9 @@ POLICY_EXPORTS = ["t1policy_conv1d_forward", "t1policy_history_rows", "t1policy_
                   "t1policy_slice_sum", "t1policy_linear_wgrad_workspace_bytes", "t1policy_linear_wgrad_bf16",
                   "t1policy_fold_rows", "t1policy_gather_rows", "t1policy_conv1_wgrad_f32",
                   "t1policy_linear_wgrad_f32", "t1policy_gemm_nt_f32", "t1policy_gemm_f32",
-                  "t1policy_linear_wgrad_f32x", "t1policy_conv1d_forward_packed_h", "t1policy_heads_forward_h"]
+                  "t1policy_linear_wgrad_f32x", "t1policy_conv1d_forward_packed_h", "t1policy_heads_forward_h",
+                  "t1policy_actor_forward", "t1policy_actor_forward_h", "t1policy_critic_forward",
+                  "t1policy_critic_forward_h"]
 
 _lib = None
 
@@ -152,6 +154,10 @@ def load():
         "t1policy_heads_frag_bytes": ([], C.c_int),
         "t1policy_heads_pack": ([vp, vp, vp, vp], C.c_int),
         "t1policy_heads_forward": ([vp, vp, vp, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp], C.c_int),
+        "t1policy_actor_forward": ([vp, vp, vp, vp, vp, i32, vp, vp, i32, vp], C.c_int),
+        "t1policy_actor_forward_h": ([vp, vp, vp, vp, vp, i32, vp, vp, i32, vp], C.c_int),
+        "t1policy_critic_forward": ([vp, vp, vp, vp, i32, vp, i32, vp], C.c_int),
+        "t1policy_critic_forward_h": ([vp, vp, vp, vp, i32, vp, i32, vp], C.c_int),
         "t1policy_conv1_bf16_frag_bytes": ([], C.c_int),
         "t1policy_conv1_bf16_workspace_bytes": ([], C.c_int),
         "t1policy_conv1_pack_bf16": ([vp, vp, i32, i32, i32, vp], C.c_int),

@@ -15,6 +15,7 @@ Same architecture, parameter names and initialisation as the reference, so its c
 through PyTorch-ROCm; the per-step inference batch is every env on the rank.
 """
 import contextlib
+import os
 
 import torch
 import torch.nn as nn
@@ -713,6 +714,71 @@ def heads_forward(ac, obs, critic_obs, eps):
     return (mean, actions, sigma, logp, value) if rc == 0 else None
 
 
+def _heads_ready(ac, x):
+    """The model and dtype refusals heads_forward takes, for the one 2-d input x of a one-role entry: the model's 15
+    layers when the fused kernels can read x and the parameters, else None (the caller checks x's width)."""
+    layers = _heads_layers(ac)
+    if (layers is None or not x.is_cuda or x.dtype not in (torch.float32, torch.float16) or x.dim() != 2
+            or _heads_args(ac, layers) is None or ac.std.device != x.device):
+        return None
+    return layers
+
+
+def actor_forward(ac, obs):
+    """The deterministic policy as the fused HIP kernels (the packed first conv, then t1policy_actor_forward[_h]: the
+    heads kernel's actor chain alone): (action mean (B, 12), estimated base velocity (B, 3)) -- act_inference's result
+    and the exported module's second output -- or None when the model or obs has no compiled instance (the caller keeps
+    torch's layers).  obs (B, 66 * 47) fp32 or fp16 (the env's fp16 histories, read in place); the mean is
+    heads_forward's bit for bit.  The weights are packed as there (packed_heads_weights)."""
+    if _heads_ready(ac, obs) is None or obs.shape[1] != ac.in_channels * ac.num_proprio_obs:
+        return None
+    dev = obs.device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    obs = obs.contiguous()
+    B = obs.shape[0]
+    y1 = conv1d_direct(obs.view(B, ac.in_channels, ac.num_proprio_obs), ac.long_history[0])
+    if y1 is None:
+        return None
+    packed = packed_heads_weights(ac, stream)
+    if packed is None:
+        return None
+    frag, ptrs_c, dims_c = packed
+    mean = torch.empty(B, ac.std.numel(), device=dev)
+    est = torch.empty(B, 3, device=dev)
+    entry = "t1policy_actor_forward_h" if obs.dtype == torch.float16 else "t1policy_actor_forward"
+    rc = _call(entry, ptrs_c, dims_c, frag.data_ptr(), y1.data_ptr(), obs.data_ptr(), obs.shape[1], mean.data_ptr(),
+               est.data_ptr(), B, stream, refusals=(1,))
+    return (mean, est) if rc == 0 else None
+
+
+def critic_forward(ac, critic_obs):
+    """The critic's value (B, 1) as the fused HIP kernel (t1policy_critic_forward[_h]: the heads kernel's critic chain
+    alone; heads_forward's value bit for bit), or None as actor_forward.  critic_obs (B, 219) fp32 or fp16."""
+    layers = _heads_ready(ac, critic_obs)
+    if layers is None or critic_obs.shape[1] != layers[11].in_features:
+        return None
+    dev = critic_obs.device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    packed = packed_heads_weights(ac, stream)
+    if packed is None:
+        return None
+    frag, ptrs_c, dims_c = packed
+    critic_obs = critic_obs.contiguous()
+    B = critic_obs.shape[0]
+    value = torch.empty(B, 1, device=dev)
+    entry = "t1policy_critic_forward_h" if critic_obs.dtype == torch.float16 else "t1policy_critic_forward"
+    rc = _call(entry, ptrs_c, dims_c, frag.data_ptr(), critic_obs.data_ptr(), critic_obs.shape[1], value.data_ptr(), B,
+               stream, refusals=(1,))
+    return value if rc == 0 else None
+
+
+def fused_inference_enabled(x):
+    """The fused inference kernels may serve x: no autograd graph is being recorded (no_grad / inference_mode), x is on
+    the device in fp32 or fp16, and T1_FUSED_INFERENCE is not "0" (A/B: torch's layers)."""
+    return (not torch.is_grad_enabled() and x.is_cuda and x.dtype in (torch.float32, torch.float16)
+            and os.environ.get("T1_FUSED_INFERENCE") != "0")
+
+
 class _UnfoldRows(torch.autograd.Function):
     """The (B * Lout, C * k) window rows of a channels-last (B, L, C) device tensor (x.unfold(1, k, st), copied); the
     backward is the HIP gather t1policy_fold_rows -- each input element sums its (at most k / st) window entries in
@@ -865,7 +931,24 @@ class ActorCriticDH(nn.Module):
         return self.distribution.log_prob(actions).sum(dim=-1)
 
     def act_inference(self, observations):
+        """The deterministic policy.  Without autograd on the device: the fused HIP kernels (actor_forward), fp16
+        observation histories included; else -- on the host, with grad enabled, under T1_FUSED_INFERENCE=0, or for a
+        model without a compiled instance -- torch's layers."""
+        if fused_inference_enabled(observations):
+            out = actor_forward(self, observations)
+            if out is not None:
+                return out[0]
         return self.actor(self.actor_input(observations))
+
+    def act_inference_with_velocity(self, observations):
+        """(action mean, estimated base linear velocity): the two outputs of the exported module
+        (scripts/export_policy.py ExportedDH), on the same two paths as act_inference."""
+        if fused_inference_enabled(observations):
+            out = actor_forward(self, observations)
+            if out is not None:
+                return out
+        est_vel = self.state_estimator(observations[..., -self.num_short_obs:])
+        return self.actor(self.actor_input(observations, es_vel=est_vel)), est_vel
 
     def evaluate(self, critic_observations, **kwargs):
         return self.critic(critic_observations).float()

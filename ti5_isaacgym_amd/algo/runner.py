@@ -15,12 +15,14 @@ import json
 import os
 import statistics
 import time
+import warnings
 from collections import deque
 
 import torch
 
 from . import distributed as dist_util
-from .dh_policy import ActorCriticDH
+from .dh_policy import (ActorCriticDH, actor_forward, critic_forward, fused_inference_enabled,
+                        refresh_packed_weights)
 from .dh_update import DHPPO
 
 POLICY_CLASSES = {"ActorCriticDH": ActorCriticDH}
@@ -212,14 +214,77 @@ class DHOnPolicyRunner:
         self.current_learning_iteration = d["iter"]
         return d["infos"]
 
-    def get_inference_policy(self, device=None):
+    def get_inference_policy(self, device=None, graphed=False):
+        """The deterministic policy (ActorCriticDH.act_inference: the fused HIP kernels without autograd on the
+        device).  graphed: a callable that replays the first conv and the actor kernel as one captured HIP graph per
+        observation buffer (GraphedInference)."""
         self.alg.actor_critic.eval()
         if device is not None:
             self.alg.actor_critic.to(device)
+        if graphed:
+            return GraphedInference(self.alg.actor_critic)
         return self.alg.actor_critic.act_inference
 
     def get_inference_critic(self, device=None):
-        self.alg.actor_critic.eval()
+        """The critic's value: the fused HIP kernel (dh_policy.critic_forward) without autograd on the device, else
+        ActorCriticDH.evaluate (which the update and compute_returns keep calling as it is)."""
+        ac = self.alg.actor_critic
+        ac.eval()
         if device is not None:
-            self.alg.actor_critic.to(device)
-        return self.alg.actor_critic.evaluate
+            ac.to(device)
+
+        def critic(critic_observations, **kwargs):
+            if fused_inference_enabled(critic_observations):
+                value = critic_forward(ac, critic_observations)
+                if value is not None:
+                    return value
+            return ac.evaluate(critic_observations, **kwargs)
+        return critic
+
+
+class GraphedInference:
+    """act_inference as a captured HIP graph (the packed first conv + the actor kernel) per observation buffer, keyed on
+    (data_ptr, shape, dtype) as DHPPO._graphed_act: the env's ping-pong pair gives two graphs; a buffer past the fourth
+    key, a call with autograd on, off the device, or one the fused kernels refuse runs eager act_inference.  The packed
+    weights are refreshed before each replay (an in-place weight change shows in the next call); a failed capture falls
+    back to eager for good.  The returned mean is the graph's output buffer: overwritten by the next call on the same
+    observation buffer."""
+
+    MAX_GRAPHS = 4
+
+    def __init__(self, actor_critic):
+        self.ac = actor_critic
+        self.graphs = {}
+        self.enabled = True
+
+    def __call__(self, obs):
+        ac = self.ac
+        if not (self.enabled and fused_inference_enabled(obs)):
+            return ac.act_inference(obs)
+        key = (obs.data_ptr(), tuple(obs.shape), obs.dtype)
+        entry = self.graphs.get(key)
+        if entry is None:
+            if len(self.graphs) >= self.MAX_GRAPHS:   # not the env's fixed buffers: stay eager
+                return ac.act_inference(obs)
+            with torch.no_grad():
+                side = torch.cuda.Stream(device=obs.device)
+                side.wait_stream(torch.cuda.current_stream(obs.device))
+                with torch.cuda.stream(side):   # warm-up outside the capture (allocator, the weight pack)
+                    for _ in range(2):
+                        out = actor_forward(ac, obs)
+                torch.cuda.current_stream(obs.device).wait_stream(side)
+                if out is None:   # no compiled instance: torch's layers, never captured
+                    self.enabled = False
+                    return ac.act_inference(obs)
+                graph = torch.cuda.CUDAGraph()
+                try:
+                    with torch.cuda.graph(graph):
+                        out = actor_forward(ac, obs)
+                except RuntimeError as e:
+                    warnings.warn(f"GraphedInference: graph capture failed, running eager: {e}")
+                    self.enabled = False
+                    return ac.act_inference(obs)
+            entry = self.graphs[key] = (graph, out, obs)   # obs: the buffer stays alive with its graph
+        refresh_packed_weights(ac)
+        entry[0].replay()
+        return entry[1][0]

@@ -7,7 +7,9 @@
 //   critic             privileged (219) -> 768 ELU -> 256 ELU -> 128 ELU -> 1                   (:60-73, :185-188)
 //
 // plus the Normal sample, its log-prob and the broadcast sigma (DHPPO._act_body), from the first conv's output
-// (t1policy_conv1d_forward_packed), the actor and critic observations and a standard-normal draw.
+// (t1policy_conv1d_forward_packed), the actor and critic observations and a standard-normal draw.  The same kernel
+// runs the deterministic policy (act_inference: the actor chain alone, the mean and the estimated velocity) and the
+// critic's value (evaluate) as one-role launches (t1policy_actor_forward / t1policy_critic_forward, k_heads64's ROLE).
 //
 // A workgroup owns 64 envs (k_heads64, the default: two 32-env column tiles sharing every weight fragment, below) or
 // 32 (k_heads, A/B) and one role (actor chain or critic), eight waves (two per SIMD) splitting each layer's
@@ -334,7 +336,7 @@ __device__ __forceinline__ void ph_stage(Frag* dst, int steps, const float* __re
   }
 }
 
-enum { OUT_LDS = 0, OUT_LDS_HALF = 1, OUT_MEAN = 2, OUT_VALUE = 3 };
+enum { OUT_LDS = 0, OUT_LDS_HALF = 1, OUT_MEAN = 2, OUT_VALUE = 3, OUT_MEAN_ONLY = 4, OUT_LDS_HALF_EST = 5 };
 
 struct PhOut {  // the global outputs (OUT_MEAN / OUT_VALUE layers)
   const float* eps;
@@ -616,9 +618,12 @@ void k_heads(PhParams P, const h8* __restrict__ frag, const float* __restrict__ 
 // next layer's accumulators (held in registers across the calls) before the next one overwrites it; the short
 // history is staged twice (the estimator's first layer, then the actor's).  Every layer call has one output tile per
 // wave (8 waves, T = 1).
-typedef h8 Frag2[2][2][64];  // one k-step of B fragments of both 32-env tiles: [env tile][hi, lo][lane]
-struct Heads64Lds {
-  Frag2 px[36];  // actor: PX[0..35]; critic: PX[0..31] (layout per phase in k_heads64)
+// ET: the 32-env column tiles of a workgroup.  2 = the 64-env workgroup above (act(), and the one-role inference
+// launches past one 32-env tile per CU); 1 = a 32-env workgroup with the same layer calls, k order and epilogues per env
+// column (the one-role inference launches up to one tile per CU: half the MFMAs per fragment, 72 KB of LDS).
+template <int ET> using FragE = h8[ET][2][64];  // one k-step of B fragments of the ET env tiles: [env tile][hi, lo][lane]
+template <int ET> struct HeadsLds {
+  FragE<ET> px[36];  // actor: PX[0..35]; critic: PX[0..31] (layout per phase in ph6_actor / ph6_critic)
 };
 
 // one layer call: layer L's output tiles [TB, TB + 8) (or to the layer's last tile) over its k-steps [KB, KE)
@@ -653,6 +658,7 @@ struct PhOut64 {  // the global outputs and the workgroup's envs
   float* sigma;
   float* logp;
   float* value;
+  float* est;  // (batch, 3): the state estimator's output (the actor-only launch; unused otherwise)
   int env0;
   int batch;
 };
@@ -662,13 +668,13 @@ struct PhOut64 {  // the global outputs and the workgroup's envs
 // lo part is exactly 0 -- what split8 makes of the widened value, so the staged fragments are the fp32 path's on
 // obs.float() bit for bit (finite values) -- read by 16-bit loads: its rows are 2-byte aligned only (an obs row's short
 // history starts at half 2867 of a 6204-byte row, a critic row is 438 B).
-template <bool RELU, typename T>
-__device__ __forceinline__ void ph6_stage(Frag2* dst, int steps, const T* __restrict__ src, long long stride,
+template <bool RELU, int ET, typename T>
+__device__ __forceinline__ void ph6_stage(FragE<ET>* dst, int steps, const T* __restrict__ src, long long stride,
                                           int col0, int len, int env0, int batch, int wave, int lane) {
   const int h = lane >> 5;
   for (int s = wave; s < steps; s += PH_WAVES) {
 #pragma unroll
-    for (int et = 0; et < 2; ++et) {
+    for (int et = 0; et < ET; ++et) {
       const int env = env0 + 32 * et + (lane & 31);
       const bool live = env < batch;
       const T* row = src + (long long)(live ? env : batch - 1) * stride + col0;
@@ -703,24 +709,24 @@ __device__ __forceinline__ void ph6_stage(Frag2* dst, int steps, const T* __rest
 // previous call), six MFMAs per k-step into acc (ZERO: start from 0; the caller owns acc, so a layer split over calls
 // keeps its sums); EPI: result + bias through the activation into out (k-steps out0 + 2 (tile - TB) + {0, 1}) or the
 // global outputs.  NX: the next call's ring, whose first fragments are issued before this call's epilogue.
-template <class RG, int OUT, bool ZERO, bool EPI, class NX>
-__device__ __forceinline__ void ph6_call(const h8* __restrict__ frag, const Frag2* in, Frag2* out, int out0,
-                                         const PhOut64& G, int wave, int lane, RG& rg, NX* nx, f16v (&acc0)[2],
-                                         f16v (&acc1)[2]) {
+template <class RG, int OUT, bool ZERO, bool EPI, class NX, int ET>
+__device__ __forceinline__ void ph6_call(const h8* __restrict__ frag, const FragE<ET>* in, FragE<ET>* out, int out0,
+                                         const PhOut64& G, int wave, int lane, RG& rg, NX* nx, f16v (&acc0)[ET],
+                                         f16v (&acc1)[ET]) {
   constexpr Layer Y = PH_L[RG::L];
   constexpr int KL = RG::KL, D = RG::D, R = RG::R;
   const int h = lane >> 5;
   const bool busy = wave < RG::NW;  // wave-uniform
   if constexpr (ZERO) {
 #pragma unroll
-    for (int et = 0; et < 2; ++et)
+    for (int et = 0; et < ET; ++et)
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc0[et][r] = acc1[et][r] = 0.0f;
   }
   float4 bias[4];
-  h8 bq[2][2][2];  // [buffer][env tile][hi, lo]
+  h8 bq[2][ET][2];  // [buffer][env tile][hi, lo]
 #pragma unroll
-  for (int et = 0; et < 2; ++et) {
+  for (int et = 0; et < ET; ++et) {
     bq[0][et][0] = in[0][et][0][lane];
     bq[0][et][1] = in[0][et][1][lane];
   }
@@ -735,7 +741,7 @@ __device__ __forceinline__ void ph6_call(const h8* __restrict__ frag, const Frag
       }
       if (s + 1 < KL) {
 #pragma unroll
-        for (int et = 0; et < 2; ++et) {
+        for (int et = 0; et < ET; ++et) {
           bq[(s + 1) & 1][et][0] = in[s + 1][et][0][lane];
           bq[(s + 1) & 1][et][1] = in[s + 1][et][1][lane];
         }
@@ -743,7 +749,7 @@ __device__ __forceinline__ void ph6_call(const h8* __restrict__ frag, const Frag
       __builtin_amdgcn_sched_barrier(0);
       const h8 ah = rg.w[s % R][0], al = rg.w[s % R][1];
 #pragma unroll
-      for (int et = 0; et < 2; ++et) {
+      for (int et = 0; et < ET; ++et) {
         const h8 bh = bq[s & 1][et][0], bl = bq[s & 1][et][1];
         acc0[et] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc0[et], 0, 0, 0);
         acc1[et] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc1[et], 0, 0, 0);
@@ -756,7 +762,7 @@ __device__ __forceinline__ void ph6_call(const h8* __restrict__ frag, const Frag
     if (!busy) return;
     const int nt = RG::TB + wave;
 #pragma unroll
-    for (int et = 0; et < 2; ++et) {
+    for (int et = 0; et < ET; ++et) {
       float v[16];
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
@@ -766,7 +772,13 @@ __device__ __forceinline__ void ph6_call(const h8* __restrict__ frag, const Frag
       }
       const int env = G.env0 + 32 * et + (lane & 31);
       const bool live = env < G.batch;
-      if constexpr (OUT == OUT_LDS || OUT == OUT_LDS_HALF) {
+      if constexpr (OUT == OUT_LDS || OUT == OUT_LDS_HALF || OUT == OUT_LDS_HALF_EST) {
+        if constexpr (OUT == OUT_LDS_HALF_EST) {  // the estimate (rows 0-2: registers 0-2 of lane half 0) before the split
+          if (h == 0 && live) {
+#pragma unroll
+            for (int r = 0; r < 3; ++r) G.est[(size_t)env * 3 + r] = v[r];
+          }
+        }
 #pragma unroll
         for (int s = 0; s < (OUT == OUT_LDS ? 2 : 1); ++s) {
           float u[8];
@@ -776,6 +788,12 @@ __device__ __forceinline__ void ph6_call(const h8* __restrict__ frag, const Frag
           split8(u, hi, lo);
           out[out0 + 2 * (nt - RG::TB) + s][et][0][lane] = hi;
           out[out0 + 2 * (nt - RG::TB) + s][et][1][lane] = lo;
+        }
+      } else if constexpr (OUT == OUT_MEAN_ONLY) {  // the deterministic policy: the mean alone (no eps, std, sample)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+          if (row < Y.n && live) G.mean[(size_t)env * Y.n + row] = v[r];
         }
       } else if constexpr (OUT == OUT_MEAN) {  // as ph_layer's OUT_MEAN
         float lp = 0.0f;
@@ -805,101 +823,129 @@ __device__ __forceinline__ void ph6_call(const h8* __restrict__ frag, const Frag
 template <int L, int KB, int KE, int TB = 0> using R6 = P6Ring<L, KB, KE, TB>;
 template <int L> using R6F = P6Ring<L, 0, PH_L[L].ks, 0>;  // a whole layer
 
-// TO: the element type of obs and cobs (float, or _Float16: t1policy_heads_forward_h); y1 is fp32 either way
-template <typename TO>
+// the actor chain of one workgroup (history tail, state estimator, actor) on its ET env tiles.  TO: the element type of
+// obs (float, or _Float16: the _h entries); y1 is fp32 either way.  DET: the deterministic policy (act_inference) --
+// the last epilogue writes the mean alone and layer 6's also stores the estimate to G.est.
+template <typename TO, int ET, bool DET>
+__device__ __forceinline__ void ph6_actor(const h8* __restrict__ frag, const float* __restrict__ y1,
+                                          const TO* __restrict__ obs, int obs_cols, FragE<ET>* X, const PhOut64& G,
+                                          int batch, int wave, int lane) {
+  f16v a0[ET], a1[ET];  // the current call's accumulators
+  f16v b0[ET], b1[ET];  // the layer after a split one: its sums across the split layer's calls
+  // PX[0..27] the relu'd conv1 output; L0 -> PX[28..33]; L1 -> PX[0..7]; short history -> PX[16..30]; L2 (the
+  // history code) -> PX[32..35]; L3 -> PX[0..15]; L4 -> PX[16..23]; L5 -> PX[0..3]; L6 (the estimate) -> PX[31];
+  // short history again -> PX[16..30]; the actor input is PX[16..35]; L7 halves -> PX[0..15], each into L8's sums;
+  // L8 -> PX[16..31]; L9 -> PX[0..7]; L10 -> the outputs
+  ph6_stage<true, ET>(X, 28, y1, PH_Y1, 0, PH_Y1, G.env0, batch, wave, lane);
+  R6F<0> g0;
+  ph6_prologue(frag, g0, wave, lane);
+  __syncthreads();
+  R6F<1> g1;
+  ph6_call<R6F<0>, OUT_LDS, true, true>(frag, X, X, 28, G, wave, lane, g0, &g1, a0, a1);
+  __syncthreads();
+  R6F<2> g2;
+  ph6_call<R6F<1>, OUT_LDS, true, true>(frag, X + 28, X, 0, G, wave, lane, g1, &g2, a0, a1);
+  __syncthreads();
+  ph6_stage<false, ET>(X + 16, 15, obs, obs_cols, obs_cols - PH_OBS_SHORT, PH_OBS_SHORT, G.env0, batch, wave, lane);
+  R6F<3> g3;
+  ph6_call<R6F<2>, OUT_LDS, true, true>(frag, X, X, 32, G, wave, lane, g2, &g3, a0, a1);
+  __syncthreads();
+  R6F<4> g4;
+  ph6_call<R6F<3>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g3, &g4, a0, a1);
+  __syncthreads();
+  R6F<5> g5;
+  ph6_call<R6F<4>, OUT_LDS, true, true>(frag, X, X, 16, G, wave, lane, g4, &g5, a0, a1);
+  __syncthreads();
+  R6F<6> g6;
+  ph6_call<R6F<5>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g5, &g6, a0, a1);
+  __syncthreads();
+  R6<7, 0, 20, 0> g7a;
+  ph6_call<R6F<6>, DET ? OUT_LDS_HALF_EST : OUT_LDS_HALF, true, true>(frag, X, X, 31, G, wave, lane, g6, &g7a, a0, a1);
+  ph6_stage<false, ET>(X + 16, 15, obs, obs_cols, obs_cols - PH_OBS_SHORT, PH_OBS_SHORT, G.env0, batch, wave, lane);
+  __syncthreads();
+  R6<8, 0, 16> g8a;
+  ph6_call<R6<7, 0, 20, 0>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g7a, &g8a, a0, a1);
+  __syncthreads();
+  R6<7, 0, 20, 8> g7b;
+  ph6_call<R6<8, 0, 16>, OUT_LDS, true, false>(frag, X, (FragE<ET>*)nullptr, 0, G, wave, lane, g8a, &g7b, b0, b1);
+  __syncthreads();
+  R6<8, 16, 32> g8b;
+  ph6_call<R6<7, 0, 20, 8>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g7b, &g8b, a0, a1);
+  __syncthreads();
+  R6F<9> g9;
+  ph6_call<R6<8, 16, 32>, OUT_LDS, false, true>(frag, X, X, 16, G, wave, lane, g8b, &g9, b0, b1);
+  __syncthreads();
+  R6F<10> g10;
+  ph6_call<R6F<9>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g9, &g10, a0, a1);
+  __syncthreads();
+  ph6_call<R6F<10>, DET ? OUT_MEAN_ONLY : OUT_MEAN, true, true, P6None>(frag, X, (FragE<ET>*)nullptr, 0, G, wave, lane,
+                                                                        g10, nullptr, a0, a1);
+}
+
+// the critic chain of one workgroup on its ET env tiles
+template <typename TO, int ET>
+__device__ __forceinline__ void ph6_critic(const h8* __restrict__ frag, const TO* __restrict__ cobs, int cobs_cols,
+                                           FragE<ET>* X, const PhOut64& G, int batch, int wave, int lane) {
+  f16v a0[ET], a1[ET];
+  f16v b0[ET], b1[ET];
+  // PX[16..29] the privileged observations; L11 thirds -> PX[0..15], each into L12's sums; L12 -> PX[16..31];
+  // L13 -> PX[0..7]; L14 -> the value
+  ph6_stage<false, ET>(X + 16, 14, cobs, cobs_cols, 0, PH_CRITIC, G.env0, batch, wave, lane);
+  R6<11, 0, 14, 0> g11a;
+  ph6_prologue(frag, g11a, wave, lane);
+  __syncthreads();
+  R6<12, 0, 16> g12a;
+  ph6_call<R6<11, 0, 14, 0>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g11a, &g12a, a0, a1);
+  __syncthreads();
+  R6<11, 0, 14, 8> g11b;
+  ph6_call<R6<12, 0, 16>, OUT_LDS, true, false>(frag, X, (FragE<ET>*)nullptr, 0, G, wave, lane, g12a, &g11b, b0, b1);
+  __syncthreads();
+  R6<12, 16, 32> g12b;
+  ph6_call<R6<11, 0, 14, 8>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g11b, &g12b, a0, a1);
+  __syncthreads();
+  R6<11, 0, 14, 16> g11c;
+  ph6_call<R6<12, 16, 32>, OUT_LDS, false, false>(frag, X, (FragE<ET>*)nullptr, 0, G, wave, lane, g12b, &g11c, b0, b1);
+  __syncthreads();
+  R6<12, 32, 48> g12c;
+  ph6_call<R6<11, 0, 14, 16>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g11c, &g12c, a0, a1);
+  __syncthreads();
+  R6F<13> g13;
+  ph6_call<R6<12, 32, 48>, OUT_LDS, false, true>(frag, X, X, 16, G, wave, lane, g12c, &g13, b0, b1);
+  __syncthreads();
+  R6F<14> g14;
+  ph6_call<R6F<13>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g13, &g14, a0, a1);
+  __syncthreads();
+  ph6_call<R6F<14>, OUT_VALUE, true, true, P6None>(frag, X, (FragE<ET>*)nullptr, 0, G, wave, lane, g14, nullptr, a0, a1);
+}
+
+// the roles of a launch: both (act(): actor and critic workgroups interleaved over blockIdx, the sampled policy), or one
+// (every workgroup of the grid an actor tile -- the deterministic policy and the estimate -- or a critic tile)
+enum { ROLE_BOTH = 0, ROLE_ACTOR = 1, ROLE_CRITIC = 2 };
+
+// TO: the element type of obs and cobs (float, or _Float16: the _h entries); y1 is fp32 either way
+template <typename TO, int ET = 2, int ROLE = ROLE_BOTH>
 __global__ __launch_bounds__(64 * PH_WAVES) __attribute__((amdgpu_waves_per_eu(PH_WAVES / 4, PH_WAVES / 4)))
 void k_heads64(const h8* __restrict__ frag, const float* __restrict__ y1, const TO* __restrict__ obs, int obs_cols,
                const TO* __restrict__ cobs, int cobs_cols, PhOut64 G, int batch) {
-  __shared__ Heads64Lds S;
+  __shared__ HeadsLds<ET> S;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  // both roles on every XCD (blockIdx mod 8), alternating in each XCD's dispatch order (k_heads' xcd_split 2)
   const int bid = blockIdx.x;
-  const bool critic = ((bid >> 3) & 1) != 0;
-  const int tile = ((bid >> 4) << 3) + (bid & 7);
-  G.env0 = tile * 64;
+  // ROLE_BOTH: both roles on every XCD (blockIdx mod 8), alternating in each XCD's dispatch order (k_heads' xcd_split 2)
+  const bool critic = ROLE == ROLE_BOTH ? ((bid >> 3) & 1) != 0 : ROLE == ROLE_CRITIC;
+  const int tile = ROLE == ROLE_BOTH ? ((bid >> 4) << 3) + (bid & 7) : bid;
+  G.env0 = tile * (32 * ET);
   G.batch = batch;
   if (G.env0 >= batch) return;
-  Frag2* X = S.px;
-  f16v a0[2], a1[2];  // the current call's accumulators
-  f16v b0[2], b1[2];  // the layer after a split one: its sums across the split layer's calls
-  if (!critic) {
-    // PX[0..27] the relu'd conv1 output; L0 -> PX[28..33]; L1 -> PX[0..7]; short history -> PX[16..30]; L2 (the
-    // history code) -> PX[32..35]; L3 -> PX[0..15]; L4 -> PX[16..23]; L5 -> PX[0..3]; L6 (the estimate) -> PX[31];
-    // short history again -> PX[16..30]; the actor input is PX[16..35]; L7 halves -> PX[0..15], each into L8's sums;
-    // L8 -> PX[16..31]; L9 -> PX[0..7]; L10 -> the outputs
-    ph6_stage<true>(X, 28, y1, PH_Y1, 0, PH_Y1, G.env0, batch, wave, lane);
-    R6F<0> g0;
-    ph6_prologue(frag, g0, wave, lane);
-    __syncthreads();
-    R6F<1> g1;
-    ph6_call<R6F<0>, OUT_LDS, true, true>(frag, X, X, 28, G, wave, lane, g0, &g1, a0, a1);
-    __syncthreads();
-    R6F<2> g2;
-    ph6_call<R6F<1>, OUT_LDS, true, true>(frag, X + 28, X, 0, G, wave, lane, g1, &g2, a0, a1);
-    __syncthreads();
-    ph6_stage<false>(X + 16, 15, obs, obs_cols, obs_cols - PH_OBS_SHORT, PH_OBS_SHORT, G.env0, batch, wave, lane);
-    R6F<3> g3;
-    ph6_call<R6F<2>, OUT_LDS, true, true>(frag, X, X, 32, G, wave, lane, g2, &g3, a0, a1);
-    __syncthreads();
-    R6F<4> g4;
-    ph6_call<R6F<3>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g3, &g4, a0, a1);
-    __syncthreads();
-    R6F<5> g5;
-    ph6_call<R6F<4>, OUT_LDS, true, true>(frag, X, X, 16, G, wave, lane, g4, &g5, a0, a1);
-    __syncthreads();
-    R6F<6> g6;
-    ph6_call<R6F<5>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g5, &g6, a0, a1);
-    __syncthreads();
-    R6<7, 0, 20, 0> g7a;
-    ph6_call<R6F<6>, OUT_LDS_HALF, true, true>(frag, X, X, 31, G, wave, lane, g6, &g7a, a0, a1);
-    ph6_stage<false>(X + 16, 15, obs, obs_cols, obs_cols - PH_OBS_SHORT, PH_OBS_SHORT, G.env0, batch, wave, lane);
-    __syncthreads();
-    R6<8, 0, 16> g8a;
-    ph6_call<R6<7, 0, 20, 0>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g7a, &g8a, a0, a1);
-    __syncthreads();
-    R6<7, 0, 20, 8> g7b;
-    ph6_call<R6<8, 0, 16>, OUT_LDS, true, false>(frag, X, nullptr, 0, G, wave, lane, g8a, &g7b, b0, b1);
-    __syncthreads();
-    R6<8, 16, 32> g8b;
-    ph6_call<R6<7, 0, 20, 8>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g7b, &g8b, a0, a1);
-    __syncthreads();
-    R6F<9> g9;
-    ph6_call<R6<8, 16, 32>, OUT_LDS, false, true>(frag, X, X, 16, G, wave, lane, g8b, &g9, b0, b1);
-    __syncthreads();
-    R6F<10> g10;
-    ph6_call<R6F<9>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g9, &g10, a0, a1);
-    __syncthreads();
-    ph6_call<R6F<10>, OUT_MEAN, true, true, P6None>(frag, X, nullptr, 0, G, wave, lane, g10, nullptr, a0, a1);
+  if constexpr (ROLE == ROLE_BOTH) {
+    if (!critic)
+      ph6_actor<TO, ET, false>(frag, y1, obs, obs_cols, S.px, G, batch, wave, lane);
+    else
+      ph6_critic<TO, ET>(frag, cobs, cobs_cols, S.px, G, batch, wave, lane);
+  } else if constexpr (ROLE == ROLE_ACTOR) {
+    ph6_actor<TO, ET, true>(frag, y1, obs, obs_cols, S.px, G, batch, wave, lane);
   } else {
-    // PX[16..29] the privileged observations; L11 thirds -> PX[0..15], each into L12's sums; L12 -> PX[16..31];
-    // L13 -> PX[0..7]; L14 -> the value
-    ph6_stage<false>(X + 16, 14, cobs, cobs_cols, 0, PH_CRITIC, G.env0, batch, wave, lane);
-    R6<11, 0, 14, 0> g11a;
-    ph6_prologue(frag, g11a, wave, lane);
-    __syncthreads();
-    R6<12, 0, 16> g12a;
-    ph6_call<R6<11, 0, 14, 0>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g11a, &g12a, a0, a1);
-    __syncthreads();
-    R6<11, 0, 14, 8> g11b;
-    ph6_call<R6<12, 0, 16>, OUT_LDS, true, false>(frag, X, nullptr, 0, G, wave, lane, g12a, &g11b, b0, b1);
-    __syncthreads();
-    R6<12, 16, 32> g12b;
-    ph6_call<R6<11, 0, 14, 8>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g11b, &g12b, a0, a1);
-    __syncthreads();
-    R6<11, 0, 14, 16> g11c;
-    ph6_call<R6<12, 16, 32>, OUT_LDS, false, false>(frag, X, nullptr, 0, G, wave, lane, g12b, &g11c, b0, b1);
-    __syncthreads();
-    R6<12, 32, 48> g12c;
-    ph6_call<R6<11, 0, 14, 16>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g11c, &g12c, a0, a1);
-    __syncthreads();
-    R6F<13> g13;
-    ph6_call<R6<12, 32, 48>, OUT_LDS, false, true>(frag, X, X, 16, G, wave, lane, g12c, &g13, b0, b1);
-    __syncthreads();
-    R6F<14> g14;
-    ph6_call<R6F<13>, OUT_LDS, true, true>(frag, X + 16, X, 0, G, wave, lane, g13, &g14, a0, a1);
-    __syncthreads();
-    ph6_call<R6F<14>, OUT_VALUE, true, true, P6None>(frag, X, nullptr, 0, G, wave, lane, g14, nullptr, a0, a1);
+    ph6_critic<TO, ET>(frag, cobs, cobs_cols, S.px, G, batch, wave, lane);
   }
 }
 
@@ -955,7 +1001,7 @@ int t1policy_heads_forward(const uint64_t* params, const int* dims, const void* 
   if (!ph_params(params, P)) return -1;
   const char* hv = getenv("T1POLICY_HEADS64");  // 0: the 32-env k_heads (A/B)
   if (!(hv && hv[0] == '0')) {
-    const PhOut64 G{eps, P.std, mean, actions, sigma, logp, value, 0, batch};
+    const PhOut64 G{eps, P.std, mean, actions, sigma, logp, value, nullptr, 0, batch};
     const int tiles = (batch + 63) / 64;
     hipLaunchKernelGGL(k_heads64<float>, dim3(16 * ((tiles + 7) / 8)), dim3(64 * PH_WAVES), 0, (hipStream_t)stream,
                        reinterpret_cast<const h8*>(frag), y1, obs, obs_cols, critic_obs, critic_cols, G, batch);
@@ -992,12 +1038,105 @@ int t1policy_heads_forward_h(const uint64_t* params, const int* dims, const void
   if (!ph_params(params, P)) return -1;
   const char* hv = getenv("T1POLICY_HEADS64");
   if (hv && hv[0] == '0') return 1;
-  const PhOut64 G{eps, P.std, mean, actions, sigma, logp, value, 0, batch};
+  const PhOut64 G{eps, P.std, mean, actions, sigma, logp, value, nullptr, 0, batch};
   const int tiles = (batch + 63) / 64;
   hipLaunchKernelGGL(k_heads64<_Float16>, dim3(16 * ((tiles + 7) / 8)), dim3(64 * PH_WAVES), 0, (hipStream_t)stream,
                      reinterpret_cast<const h8*>(frag), y1, reinterpret_cast<const _Float16*>(obs), obs_cols,
                      reinterpret_cast<const _Float16*>(critic_obs), critic_cols, G, batch);
   return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the env tile of a one-role launch: 32 envs per workgroup (ET 1) while every 32-env tile gets a CU of its own, 64
+// (ET 2) above that -- a workgroup's time grows with its envs (42 us at 32, 80 us at 64 in act()), but past one
+// workgroup per CU a second round of 32-env tiles costs more than 64-env tiles in one.  T1POLICY_INFER_TILE=32|64
+// overrides (A/B, tests).
+int ph_infer_et(int batch) {
+  if (const char* tv = getenv("T1POLICY_INFER_TILE")) {
+    if (atoi(tv) == 32) return 1;
+    if (atoi(tv) == 64) return 2;
+  }
+  static int cus = 0;  // the device's CU count, read once (t1env.hip reads it the same way for t1_dyn_kernel_default)
+  if (cus == 0) {
+    int dev = 0, n = 256;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
+      n = 256;
+    cus = n;
+  }
+  return (batch + 31) / 32 <= cus ? 1 : 2;
+}
+
+template <typename TO, int ROLE>
+int ph_infer_launch(const void* frag, const float* y1, const TO* obs, int obs_cols, const TO* cobs, int cobs_cols,
+                    const PhOut64& G, int batch, void* stream) {
+  const h8* f = reinterpret_cast<const h8*>(frag);
+  if (ph_infer_et(batch) == 1)
+    hipLaunchKernelGGL((k_heads64<TO, 1, ROLE>), dim3((batch + 31) / 32), dim3(64 * PH_WAVES), 0, (hipStream_t)stream,
+                       f, y1, obs, obs_cols, cobs, cobs_cols, G, batch);
+  else
+    hipLaunchKernelGGL((k_heads64<TO, 2, ROLE>), dim3((batch + 63) / 64), dim3(64 * PH_WAVES), 0, (hipStream_t)stream,
+                       f, y1, obs, obs_cols, cobs, cobs_cols, G, batch);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+template <typename TO>
+int ph_actor_forward(const uint64_t* params, const int* dims, const void* frag, const float* y1, const TO* obs,
+                     int obs_cols, float* mean, float* est_vel, int batch, void* stream) {
+  if (!params || !dims || !frag || !y1 || !obs || !mean || !est_vel || batch < 0) return -1;
+  if (!ph_dims_match(dims)) return 1;
+  if (obs_cols < PH_OBS_SHORT) return 1;
+  if (batch == 0) return 0;
+  if ((reinterpret_cast<uintptr_t>(frag) & 15u) != 0) return -1;
+  if (sizeof(TO) == 2 && (reinterpret_cast<uintptr_t>(obs) & 1u) != 0) return -1;
+  PhParams P;
+  if (!ph_params(params, P)) return -1;
+  const PhOut64 G{nullptr, nullptr, mean, nullptr, nullptr, nullptr, nullptr, est_vel, 0, batch};
+  return ph_infer_launch<TO, ROLE_ACTOR>(frag, y1, obs, obs_cols, (const TO*)nullptr, 0, G, batch, stream);
+}
+
+template <typename TO>
+int ph_critic_forward(const uint64_t* params, const int* dims, const void* frag, const TO* critic_obs,
+                      int critic_cols, float* value, int batch, void* stream) {
+  if (!params || !dims || !frag || !critic_obs || !value || batch < 0) return -1;
+  if (!ph_dims_match(dims)) return 1;
+  if (critic_cols != PH_CRITIC) return 1;
+  if (batch == 0) return 0;
+  if ((reinterpret_cast<uintptr_t>(frag) & 15u) != 0) return -1;
+  if (sizeof(TO) == 2 && (reinterpret_cast<uintptr_t>(critic_obs) & 1u) != 0) return -1;
+  PhParams P;
+  if (!ph_params(params, P)) return -1;
+  const PhOut64 G{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, value, nullptr, 0, batch};
+  return ph_infer_launch<TO, ROLE_CRITIC>(frag, nullptr, (const TO*)nullptr, 0, critic_obs, critic_cols, G, batch,
+                                          stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+// the deterministic policy and the estimate: the actor chain alone, every workgroup an actor tile (k_heads64<.., ROLE_ACTOR>)
+int t1policy_actor_forward(const uint64_t* params, const int* dims, const void* frag, const float* y1,
+                           const float* obs, int obs_cols, float* mean, float* est_vel, int batch, void* stream) {
+  return ph_actor_forward<float>(params, dims, frag, y1, obs, obs_cols, mean, est_vel, batch, stream);
+}
+int t1policy_actor_forward_h(const uint64_t* params, const int* dims, const void* frag, const float* y1,
+                             const void* obs, int obs_cols, float* mean, float* est_vel, int batch, void* stream) {
+  return ph_actor_forward<_Float16>(params, dims, frag, y1, reinterpret_cast<const _Float16*>(obs), obs_cols, mean,
+                                    est_vel, batch, stream);
+}
+// the value: the critic chain alone (k_heads64<.., ROLE_CRITIC>)
+int t1policy_critic_forward(const uint64_t* params, const int* dims, const void* frag, const float* critic_obs,
+                            int critic_cols, float* value, int batch, void* stream) {
+  return ph_critic_forward<float>(params, dims, frag, critic_obs, critic_cols, value, batch, stream);
+}
+int t1policy_critic_forward_h(const uint64_t* params, const int* dims, const void* frag, const void* critic_obs,
+                              int critic_cols, float* value, int batch, void* stream) {
+  return ph_critic_forward<_Float16>(params, dims, frag, reinterpret_cast<const _Float16*>(critic_obs), critic_cols,
+                                     value, batch, stream);
 }
 
 }  // extern "C"

@@ -1,0 +1,118 @@
+"""Run a trained checkpoint over the HIP env, headless (reference humanoid/scripts/play.py without its rendering,
+plotting and joystick: DESIGN.md §9).
+
+    python -m ti5_isaacgym_amd.scripts.play --checkpoint PATH [--num_envs 9] [--steps 2000] [--mesh_type plane]
+        [--command VX VY YAW] [--state_dtype fp32|fp16] [--robot_index 0] [--out DIR]
+
+The reference play's config changes (episode_length_s 1000, the noise curriculum off), its loop -- the deterministic
+policy (DHOnPolicyRunner.get_inference_policy(graphed=True): the first conv and the actor kernel as one replayed HIP
+graph per observation buffer), the commands held by writing env.commands before every step -- and its logs:
+
+  DIR/states.npz    one row per step for --robot_index: base_height, foot_z_l/r, foot_forcez_l/r, base_vel_x/y/z,
+                    base_vel_yaw, command_x/y/yaw (env.commands as the step read them), and per joint (steps, 12)
+                    dof_pos_target (action * action_scale), dof_pos, dof_vel, dof_torque
+  DIR/summary.json  the mean per-term episode rewards over the episodes completed during the run (extras["episode"]
+                    weighted by the envs that reset that step) and their count; also printed
+
+Every logged value stays in device buffers until the run ends: no host read per step.
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, REPO)
+
+SCALARS = ("base_height", "foot_z_l", "foot_z_r", "foot_forcez_l", "foot_forcez_r", "base_vel_x", "command_x",
+           "base_vel_y", "command_y", "base_vel_z", "base_vel_yaw", "command_yaw")
+PER_JOINT = ("dof_pos_target", "dof_pos", "dof_vel", "dof_torque")
+STATE_KEYS = SCALARS + PER_JOINT
+
+
+def parse(argv=None):
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--checkpoint", required=True)
+    p.add_argument("--num_envs", type=int, default=9)
+    p.add_argument("--steps", type=int, default=2000)
+    p.add_argument("--mesh_type", default="plane")
+    p.add_argument("--command", type=float, nargs=3, default=[0.5, 0.0, 0.0], metavar=("VX", "VY", "YAW"))
+    p.add_argument("--state_dtype", choices=["fp32", "fp16"], default="fp32")
+    p.add_argument("--robot_index", type=int, default=0)
+    p.add_argument("--out", default="play_out")
+    p.add_argument("--device", default="cuda:0")
+    p.add_argument("--seed", type=int, default=123145)
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    from ti5_isaacgym_amd import DHOnPolicyRunner, make_t1_env, task_registry
+    from ti5_isaacgym_amd.utils.helpers import class_to_dict
+    a = parse(argv)
+    if not 0 <= a.robot_index < a.num_envs:
+        raise ValueError(f"--robot_index {a.robot_index} is not one of the {a.num_envs} envs")
+
+    def hook(cfg):
+        cfg.env.episode_length_s = 1000
+        cfg.env.state_dtype = a.state_dtype
+        cfg.noise.curriculum = False
+        cfg.commands.heading_command = False
+
+    env = make_t1_env(num_envs=a.num_envs, mesh_type=a.mesh_type, seed=a.seed, device=a.device, cfg_hook=hook)
+    _, train_cfg = task_registry.get_cfgs("t1_dh_stand")
+    runner = DHOnPolicyRunner(env, class_to_dict(train_cfg), None, device=a.device)
+    runner.load(a.checkpoint, load_optimizer=False)
+    policy = runner.get_inference_policy(device=env.device, graphed=True)
+
+    dev, r, T = env.device, a.robot_index, a.steps
+    nj = env.num_actions
+    foot_l, foot_r = int(env.feet_indices[0]), int(env.feet_indices[1])
+    held = torch.tensor([*a.command, 0.0], device=dev)
+    scale = float(env.cfg.control.action_scale)
+    scalars = torch.zeros(T, len(SCALARS), device=dev)
+    joints = torch.zeros(T, len(PER_JOINT), nj, device=dev)
+    ep_keys, ep_sum = None, None
+    episodes = torch.zeros((), device=dev)
+    obs = env.get_observations()
+    with torch.inference_mode():
+        for i in range(T):
+            actions = policy(obs)
+            env.commands[:] = held
+            cmd = env.commands[r].clone()   # what this step reads
+            obs, _, _, dones, infos = env.step(actions)
+            scalars[i] = torch.stack((
+                env.root_states[r, 2], env.rigid_state[r, foot_l, 2], env.rigid_state[r, foot_r, 2],
+                env.contact_forces[r, foot_l, 2], env.contact_forces[r, foot_r, 2], env.base_lin_vel[r, 0], cmd[0],
+                env.base_lin_vel[r, 1], cmd[1], env.base_lin_vel[r, 2], env.base_ang_vel[r, 2], cmd[2]))
+            joints[i] = torch.stack((actions[r] * scale, env.dof_pos[r], env.dof_vel[r], env.torques[r]))
+            ep = infos.get("episode") or {}
+            if ep_keys is None:
+                ep_keys = [k for k, v in ep.items() if isinstance(v, torch.Tensor)]
+                ep_sum = torch.zeros(len(ep_keys), device=dev)
+            if ep_keys:   # the step's means over the envs it reset, weighted by their number
+                n = (dones > 0).sum().float()
+                vals = torch.stack([ep[k].float().reshape(()) for k in ep_keys])
+                ep_sum += torch.where(n > 0, vals * n, torch.zeros_like(vals))
+                episodes += n
+    # the one host read
+    scalars, joints = scalars.cpu().numpy(), joints.cpu().numpy()
+    count = int(episodes.item())
+    sums = ep_sum.cpu().tolist() if ep_keys else []
+    os.makedirs(a.out, exist_ok=True)
+    states = {k: scalars[:, j] for j, k in enumerate(SCALARS)}
+    states.update({k: joints[:, j] for j, k in enumerate(PER_JOINT)})
+    np.savez(os.path.join(a.out, "states.npz"), **states)
+    summary = {"checkpoint": a.checkpoint, "num_envs": a.num_envs, "steps": T, "command": list(a.command),
+               "state_dtype": a.state_dtype, "episodes": count,
+               "mean_episode": {k: (s / count if count else None) for k, s in zip(ep_keys or [], sums)}}
+    with open(os.path.join(a.out, "summary.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    print(json.dumps(summary))
+    return summary
+
+
+if __name__ == "__main__":
+    main()
