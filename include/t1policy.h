@@ -71,10 +71,9 @@ int t1policy_heads_forward(const uint64_t* params, const int* dims, const void* 
                            float* mean, float* actions, float* sigma, float* logp, float* value, int batch,
                            void* stream);
 /* t1policy_heads_forward on fp16 obs (batch, obs_cols) and fp16 critic_obs (batch, 219), any 2-byte alignment (an odd
- * address returns -1); y1, eps and every output fp32 as there; same params / dims / frag and return codes (1 also under
- * T1POLICY_HEADS64=0, which has no fp16 instance).  The kernel stages each fp16 value as its own hi part with a zero lo
- * part -- the split of the widened value -- so every output equals t1policy_heads_forward on the widened (finite)
- * inputs bit for bit (tests/test_gpu_policy_fp16_obs.py). */
+ * address returns -1); y1, eps and every output fp32 as there; same params / dims / frag and return codes.  The kernel
+ * stages each fp16 value as its own hi part with a zero lo part -- the split of the widened value -- so every output
+ * equals t1policy_heads_forward on the widened (finite) inputs bit for bit (tests/test_gpu_policy_fp16_obs.py). */
 int t1policy_heads_forward_h(const uint64_t* params, const int* dims, const void* frag, const float* y1,
                              const void* obs, int obs_cols, const void* critic_obs, int critic_cols,
                              const float* eps, float* mean, float* actions, float* sigma, float* logp,

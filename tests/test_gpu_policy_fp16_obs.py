@@ -160,10 +160,9 @@ def test_conv_fp16_odd_sample_parity_and_refused_base():
 # 33: one full 32-env tile and one env; 3000: test_gpu_policy_heads.py's ragged batch; at 96 critic_obs is base[1:], so
 # its row 0 starts 438 B into the buffer (2-byte aligned only) and the even rows are the odd-aligned ones
 @pytest.mark.parametrize("n,shifted", [(33, False), (96, True), (3000, False)])
-def test_heads_fp16_equal_fp32_heads_on_widened_inputs(n, shifted, monkeypatch):
+def test_heads_fp16_equal_fp32_heads_on_widened_inputs(n, shifted):
     from ti5_isaacgym_amd import _lib
     from ti5_isaacgym_amd.algo.dh_policy import conv1d_direct, packed_heads_weights
-    monkeypatch.delenv("T1POLICY_HEADS64", raising=False)
     _, acd = _model(1.5)
     obs, cobs, eps = [t.to(DEV) for t in _inputs(n, 300 + n)]
     if shifted:
@@ -298,7 +297,8 @@ def test_graphed_act_fp16_replays_the_eager_body():
 
 
 def test_act_body_fp16_falls_through_to_the_cast(monkeypatch):
-    """T1POLICY_HEADS64=0 (the 32-env kernel, no fp16 instance): the fp16 call is refused and the cast path answers;
+    """fp16 obs one element into its buffer (a base off a 4-byte boundary, which the fp16 conv cannot read:
+    conv1d_direct refuses): the fp16 call is refused and the cast path answers;
     FUSED_ACT off: torch's layers on the cast, and the fused path is not tried."""
     from ti5_isaacgym_amd.algo import dh_update
     from ti5_isaacgym_amd.algo.dh_policy import heads_forward
@@ -308,12 +308,14 @@ def test_act_body_fp16_falls_through_to_the_cast(monkeypatch):
     obs, cobs, eps = _inputs(n, 71)
     ref = _ref64(ac, obs.float(), cobs.float(), eps)
     obs, cobs, eps = obs.to(DEV), cobs.to(DEV), eps.to(DEV)
+    buf = torch.zeros(n * 66 * 47 + 1, dtype=torch.float16, device=DEV)
+    buf[1:] = obs.reshape(-1)
+    odd = buf[1:].view(n, 66 * 47)
+    assert odd.data_ptr() % 4 == 2 and odd.is_contiguous() and torch.equal(odd, obs)
     with torch.inference_mode():
-        monkeypatch.setenv("T1POLICY_HEADS64", "0")
-        assert heads_forward(alg.actor_critic, obs, cobs, eps) is None
-        assert heads_forward(alg.actor_critic, obs.float(), cobs.float(), eps) is not None
-        _assert_heads_close(_body(alg, obs, cobs, eps), ref)
-        monkeypatch.delenv("T1POLICY_HEADS64")
+        assert heads_forward(alg.actor_critic, odd, cobs, eps) is None
+        assert heads_forward(alg.actor_critic, odd.float(), cobs.float(), eps) is not None
+        _assert_heads_close(_body(alg, odd, cobs, eps), ref)
         monkeypatch.setattr(dh_update, "FUSED_ACT", False)
         monkeypatch.setattr(dh_update, "heads_forward", lambda *a: pytest.fail("the fused path ran with FUSED_ACT off"))
         _assert_heads_close(_body(alg, obs, cobs, eps), ref)

@@ -77,26 +77,43 @@ def test_fused_heads_match_fp64(n, scale):
     assert (value - rv).abs().max() <= 4 * (v32 - rv).abs().max() + 1e-6
 
 
-@pytest.mark.parametrize("n", [3000, 8192, 33])
-def test_heads64_equals_heads32(n, monkeypatch):
+def _gen_heads_bits():
+    import importlib.util
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gen_heads_bits.py")
+    spec = importlib.util.spec_from_file_location("gen_heads_bits", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+# 33: one full 32-env column tile and one env (the workgroup's second tile has one live lane); 545: nine 64-env tiles,
+# the ninth in the second group of 16 workgroups of k_heads64's ((bid >> 4) << 3) + (bid & 7) tile map, its tail 33 envs
+@pytest.mark.parametrize("n", [33, 545])
+def test_heads_reproduce_the_recorded_k_heads_bits(n):
     """k_heads64 (64 envs per workgroup, the 512- / 768-wide layers in halves / thirds feeding the next layer's
-    accumulators) against the 32-env k_heads (T1POLICY_HEADS64=0): the same fragments, the same k order into the same
-    fp32 accumulators per env column, so every output is bit-identical."""
+    accumulators) against the retired 32-env k_heads, which kept every layer's output in LDS: the same fragments, the
+    same k order into the same fp32 accumulators per env column, so every output is bit-identical.  k_heads' outputs
+    were recorded from the last commit that had it (tests/golden/heads_bits.npz, gen_heads_bits.py); the file also holds
+    the hashes of the inputs and the parameters they belong to."""
+    import numpy as np
     from ti5_isaacgym_amd.algo.dh_policy import heads_forward
+    gen = _gen_heads_bits()
+    assert n in gen.CASES
+    golden = np.load(gen.OUT)
     ac = _model(scale=1.5)
+    inputs = gen.inputs(n)
+    drift = "the {} drifted from the recorded ones, so the bits were not compared"
+    assert gen.digest(ac.parameters()) == str(golden["params_sha256"]), drift.format("parameters")
+    assert gen.digest(inputs) == str(golden[f"{n}_inputs_sha256"]), drift.format("inputs")
     dev = torch.device("cuda:0")
     acd = _copy(ac).to(dev)
-    g = torch.Generator().manual_seed(n + 1)
-    obs = ((torch.randn(n, 66 * 47, generator=g) * 2.0).clamp(-18, 18)).to(dev)
-    cobs = (torch.randn(n, 219, generator=g) * 2.0).to(dev)
-    eps = torch.randn(n, 12, generator=g).to(dev)
     with torch.inference_mode():
-        monkeypatch.setenv("T1POLICY_HEADS64", "1")
-        o64 = [t.clone() for t in heads_forward(acd, obs, cobs, eps)]
-        monkeypatch.setenv("T1POLICY_HEADS64", "0")
-        o32 = [t.clone() for t in heads_forward(acd, obs, cobs, eps)]
-    for name, a, b in zip(("mean", "actions", "sigma", "logp", "value"), o64, o32):
-        assert torch.equal(a, b), (name, (a - b).abs().max().item())
+        out = [t.cpu() for t in heads_forward(acd, *[t.to(dev) for t in inputs])]
+    for name, a in zip(gen.NAMES, out):
+        b = torch.from_numpy(golden[f"{n}_{name}"])
+        assert a.dtype == torch.float32 and a.shape == b.shape, name
+        assert torch.equal(a, b), (name, str(golden["commit"]), (a - b).abs().max().item())
 
 
 def test_fused_heads_propagate_nan_like_torch():

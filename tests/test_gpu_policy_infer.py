@@ -103,7 +103,6 @@ def _raw(acd, n, obs_ptr=None, obs_cols=66 * 47, cobs_ptr=None, y1=None, half=Fa
 @pytest.mark.parametrize("n", BATCHES)
 def test_one_role_launches_equal_the_act_kernel(n, monkeypatch):
     from ti5_isaacgym_amd.algo.dh_policy import actor_forward, critic_forward, heads_forward
-    monkeypatch.delenv("T1POLICY_HEADS64", raising=False)
     _, acd = _models()
     obs, cobs, eps = [t.to(DEV) for t in _inputs(n)]
     got = {}

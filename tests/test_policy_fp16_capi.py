@@ -58,8 +58,7 @@ def _heads(lib, batch=8, dims=DIMS, obs_cols=66 * 47, critic_cols=219, **ptrs):
                                         a["logp"], a["value"], batch, None)
 
 
-def test_heads_h_argument_checks(lib, monkeypatch):
-    monkeypatch.delenv("T1POLICY_HEADS64", raising=False)
+def test_heads_h_argument_checks(lib):
     for null in ("params", "dims", "frag", "y1", "obs", "critic_obs", "eps", "mean", "actions", "sigma", "logp",
                  "value"):
         assert _heads(lib, **{null: None}) == -1, null
@@ -72,6 +71,3 @@ def test_heads_h_argument_checks(lib, monkeypatch):
     assert _heads(lib, obs=ctypes.c_void_p(65)) == -1 and _heads(lib, critic_obs=ctypes.c_void_p(65)) == -1
     null_param = (ctypes.c_uint64 * 31)(*([P] * 30 + [0]))
     assert _heads(lib, params=null_param) == -1
-    # the 32-env A/B kernel has no fp16 instance: refused (1) before any launch, the caller widens
-    monkeypatch.setenv("T1POLICY_HEADS64", "0")
-    assert _heads(lib, obs=ctypes.c_void_p(66), critic_obs=ctypes.c_void_p(70)) == 1

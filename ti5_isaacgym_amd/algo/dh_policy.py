@@ -671,6 +671,36 @@ def _heads_layers(ac):
     return layers if len(layers) == 15 else None
 
 
+def _heads_ready(ac, obs=None, critic_obs=None):
+    """What heads_forward, actor_forward and critic_forward do before their launch, on the contiguous 2-d inputs each
+    has (obs, critic_obs or both): the model, dtype and shape refusals, the first conv on obs, the packed weights.
+    Returns (y1, frag, ptrs, dims, stream, suffix) -- y1 the conv's output (None without obs), suffix "_h" for fp16
+    inputs, else "" -- or None when the model or the inputs have no compiled instance.  The kernels read obs and
+    critic_obs row by row up to the batch: shapes they were not built for are refused here, not read out of bounds on
+    the device; obs and critic_obs are both fp32 or both fp16."""
+    x = obs if obs is not None else critic_obs
+    layers = _heads_layers(ac)
+    if (layers is None or not x.is_cuda or x.dtype not in (torch.float32, torch.float16) or x.dim() != 2
+            or _heads_args(ac, layers) is None or ac.std.device != x.device):
+        return None
+    if obs is not None and obs.shape[1] != ac.in_channels * ac.num_proprio_obs:
+        return None
+    if critic_obs is not None and (critic_obs.dtype != x.dtype or critic_obs.dim() != 2
+                                   or critic_obs.shape[0] != x.shape[0]
+                                   or critic_obs.shape[1] != layers[11].in_features):
+        return None
+    stream = torch.cuda.current_stream(x.device).cuda_stream
+    y1 = None
+    if obs is not None:
+        y1 = conv1d_direct(obs.view(obs.shape[0], ac.in_channels, ac.num_proprio_obs), ac.long_history[0])
+        if y1 is None:
+            return None
+    packed = packed_heads_weights(ac, stream)   # repacked only when a parameter changed
+    if packed is None:
+        return None
+    return (y1, *packed, stream, "_h" if x.dtype == torch.float16 else "")
+
+
 def heads_forward(ac, obs, critic_obs, eps):
     """The rollout's act() after the first conv as the fused HIP kernel (t1policy_heads_forward): returns mean,
     actions = mean + std eps, sigma (B, 12), log-prob (B,) and value (B, 1) -- DHPPO._act_body's outputs -- or None
@@ -679,49 +709,22 @@ def heads_forward(ac, obs, critic_obs, eps):
     results of the fp32 kernels on the widened inputs); mixed dtypes return None.  The weights are packed
     into the kernel's split fp16 fragments when a parameter changed (packed_heads_weights); a captured act() graph
     reads them in place and is refreshed before each replay."""
-    layers = _heads_layers(ac)
-    if (layers is None or not obs.is_cuda or obs.dtype not in (torch.float32, torch.float16)
-            or critic_obs.dtype != obs.dtype or obs.dim() != 2 or critic_obs.dim() != 2 or eps.shape != (obs.shape[0], ac.std.numel())):
+    if obs.dim() != 2 or eps.shape != (obs.shape[0], ac.std.numel()):
         return None
-    # the kernel reads critic_obs and obs row by row up to the batch: shapes it was not built for are refused here,
-    # not read out of bounds on the device (ADVICE r4)
-    if (critic_obs.shape[0] != obs.shape[0] or obs.shape[1] != ac.in_channels * ac.num_proprio_obs
-            or critic_obs.shape[1] != layers[11].in_features):
+    obs, critic_obs, eps = obs.contiguous(), critic_obs.contiguous(), eps.contiguous()
+    ready = _heads_ready(ac, obs, critic_obs)
+    if ready is None:
         return None
-    if _heads_args(ac, layers) is None or ac.std.device != obs.device:
-        return None
-    dev = obs.device
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    obs = obs.contiguous()
-    B = obs.shape[0]
-    y1 = conv1d_direct(obs.view(B, ac.in_channels, ac.num_proprio_obs), ac.long_history[0])
-    if y1 is None:
-        return None
-    packed = packed_heads_weights(ac, stream)   # repacked only when a parameter changed
-    if packed is None:
-        return None
-    frag, ptrs_c, dims_c = packed
-    critic_obs, eps = critic_obs.contiguous(), eps.contiguous()
-    na = ac.std.numel()
-    mean = torch.empty(B, na, device=dev)
+    y1, frag, ptrs_c, dims_c, stream, h = ready
+    B, dev = obs.shape[0], obs.device
+    mean = torch.empty(B, ac.std.numel(), device=dev)
     actions, sigma = torch.empty_like(mean), torch.empty_like(mean)
     logp = torch.empty(B, device=dev)
     value = torch.empty(B, 1, device=dev)
-    entry = "t1policy_heads_forward_h" if obs.dtype == torch.float16 else "t1policy_heads_forward"
-    rc = _call(entry, ptrs_c, dims_c, frag.data_ptr(), y1.data_ptr(), obs.data_ptr(), obs.shape[1],
-               critic_obs.data_ptr(), critic_obs.shape[1], eps.data_ptr(), mean.data_ptr(), actions.data_ptr(),
-               sigma.data_ptr(), logp.data_ptr(), value.data_ptr(), B, stream, refusals=(1,))
+    rc = _call("t1policy_heads_forward" + h, ptrs_c, dims_c, frag.data_ptr(), y1.data_ptr(), obs.data_ptr(),
+               obs.shape[1], critic_obs.data_ptr(), critic_obs.shape[1], eps.data_ptr(), mean.data_ptr(),
+               actions.data_ptr(), sigma.data_ptr(), logp.data_ptr(), value.data_ptr(), B, stream, refusals=(1,))
     return (mean, actions, sigma, logp, value) if rc == 0 else None
-
-
-def _heads_ready(ac, x):
-    """The model and dtype refusals heads_forward takes, for the one 2-d input x of a one-role entry: the model's 15
-    layers when the fused kernels can read x and the parameters, else None (the caller checks x's width)."""
-    layers = _heads_layers(ac)
-    if (layers is None or not x.is_cuda or x.dtype not in (torch.float32, torch.float16) or x.dim() != 2
-            or _heads_args(ac, layers) is None or ac.std.device != x.device):
-        return None
-    return layers
 
 
 def actor_forward(ac, obs):
@@ -730,45 +733,31 @@ def actor_forward(ac, obs):
     and the exported module's second output -- or None when the model or obs has no compiled instance (the caller keeps
     torch's layers).  obs (B, 66 * 47) fp32 or fp16 (the env's fp16 histories, read in place); the mean is
     heads_forward's bit for bit.  The weights are packed as there (packed_heads_weights)."""
-    if _heads_ready(ac, obs) is None or obs.shape[1] != ac.in_channels * ac.num_proprio_obs:
-        return None
-    dev = obs.device
-    stream = torch.cuda.current_stream(dev).cuda_stream
     obs = obs.contiguous()
+    ready = _heads_ready(ac, obs=obs)
+    if ready is None:
+        return None
+    y1, frag, ptrs_c, dims_c, stream, h = ready
     B = obs.shape[0]
-    y1 = conv1d_direct(obs.view(B, ac.in_channels, ac.num_proprio_obs), ac.long_history[0])
-    if y1 is None:
-        return None
-    packed = packed_heads_weights(ac, stream)
-    if packed is None:
-        return None
-    frag, ptrs_c, dims_c = packed
-    mean = torch.empty(B, ac.std.numel(), device=dev)
-    est = torch.empty(B, 3, device=dev)
-    entry = "t1policy_actor_forward_h" if obs.dtype == torch.float16 else "t1policy_actor_forward"
-    rc = _call(entry, ptrs_c, dims_c, frag.data_ptr(), y1.data_ptr(), obs.data_ptr(), obs.shape[1], mean.data_ptr(),
-               est.data_ptr(), B, stream, refusals=(1,))
+    mean = torch.empty(B, ac.std.numel(), device=obs.device)
+    est = torch.empty(B, 3, device=obs.device)
+    rc = _call("t1policy_actor_forward" + h, ptrs_c, dims_c, frag.data_ptr(), y1.data_ptr(), obs.data_ptr(),
+               obs.shape[1], mean.data_ptr(), est.data_ptr(), B, stream, refusals=(1,))
     return (mean, est) if rc == 0 else None
 
 
 def critic_forward(ac, critic_obs):
     """The critic's value (B, 1) as the fused HIP kernel (t1policy_critic_forward[_h]: the heads kernel's critic chain
     alone; heads_forward's value bit for bit), or None as actor_forward.  critic_obs (B, 219) fp32 or fp16."""
-    layers = _heads_ready(ac, critic_obs)
-    if layers is None or critic_obs.shape[1] != layers[11].in_features:
-        return None
-    dev = critic_obs.device
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    packed = packed_heads_weights(ac, stream)
-    if packed is None:
-        return None
-    frag, ptrs_c, dims_c = packed
     critic_obs = critic_obs.contiguous()
+    ready = _heads_ready(ac, critic_obs=critic_obs)
+    if ready is None:
+        return None
+    _, frag, ptrs_c, dims_c, stream, h = ready
     B = critic_obs.shape[0]
-    value = torch.empty(B, 1, device=dev)
-    entry = "t1policy_critic_forward_h" if critic_obs.dtype == torch.float16 else "t1policy_critic_forward"
-    rc = _call(entry, ptrs_c, dims_c, frag.data_ptr(), critic_obs.data_ptr(), critic_obs.shape[1], value.data_ptr(), B,
-               stream, refusals=(1,))
+    value = torch.empty(B, 1, device=critic_obs.device)
+    rc = _call("t1policy_critic_forward" + h, ptrs_c, dims_c, frag.data_ptr(), critic_obs.data_ptr(),
+               critic_obs.shape[1], value.data_ptr(), B, stream, refusals=(1,))
     return value if rc == 0 else None
 
 

@@ -11,10 +11,10 @@
 // runs the deterministic policy (act_inference: the actor chain alone, the mean and the estimated velocity) and the
 // critic's value (evaluate) as one-role launches (t1policy_actor_forward / t1policy_critic_forward, k_heads64's ROLE).
 //
-// A workgroup owns 64 envs (k_heads64, the default: two 32-env column tiles sharing every weight fragment, below) or
-// 32 (k_heads, A/B) and one role (actor chain or critic), eight waves (two per SIMD) splitting each layer's
-// 32-output tiles; every layer is a chain of
-// v_mfma_f32_32x32x16_f16 with the WEIGHTS as the A operand (32 output features x 16 inputs) and the ACTIVATIONS as
+// One kernel, k_heads64<TO, ET, ROLE>.  A workgroup owns ET 32-env column tiles -- 64 envs (ET 2: act(), and the larger
+// one-role launches; the two tiles share every weight fragment, below) or 32 (ET 1: the smaller one-role launches) --
+// and one role (actor chain or critic), eight waves (two per SIMD) splitting each layer's 32-output tiles.  Every layer
+// is a chain of v_mfma_f32_32x32x16_f16 with the WEIGHTS as the A operand (32 output features x 16 inputs) and the ACTIVATIONS as
 // the B operand (16 inputs x 32 envs), so a layer's 32 x 32 result has the env on the lane and the features in the
 // 16 accumulator registers -- exactly the B fragments of the next layer's two k-steps (permuted k order, cdna guide
 // "An accumulator tile as the next MFMA's operand"): an output tile goes to LDS as two 1-KB fragments per precision
@@ -43,24 +43,10 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f16v __attribute__((ext_vector_type(16)));
 
 constexpr float PH_SPLIT = 2048.0f;
-constexpr int PH_M = 32;      // envs per workgroup (one MFMA column tile)
-// waves per workgroup: 8 = two per SIMD, each with half the output tiles and a shallower fragment ring (act() 0.177 ->
-// 0.147 ms at 8192 envs, profiles/r05h8_*); 4 = one per SIMD, the round-4 kernel (A/B)
-#ifndef T1_HEADS_WAVES
-#define T1_HEADS_WAVES 8
-#endif
-constexpr int PH_WAVES = T1_HEADS_WAVES;
-// 8-wave ring depths (k-steps in flight) for 1, 2 and >= 3 output tiles per wave: act() 0.1419 ms at 4 / 2 / 1 against
-// 0.1428 at 6 / 3 / 2, 0.1443 at 8 / 4 / 2 and 0.1470 at 12 / 6 / 2 (profiles/r05hd_act_ab.txt; A/B)
-#ifndef T1_HEADS_D1
-#define T1_HEADS_D1 4
-#endif
-#ifndef T1_HEADS_D2
-#define T1_HEADS_D2 2
-#endif
-#ifndef T1_HEADS_D3
-#define T1_HEADS_D3 1
-#endif
+// waves per workgroup, two per SIMD: act() 0.177 -> 0.147 ms at 8192 envs against one per SIMD (profiles/r05h8_*)
+constexpr int PH_WAVES = 8;
+// ring depth in k-steps: act() 0.1419 ms at 4, 0.1428 at 6, 0.1443 at 8, 0.1470 at 12 (profiles/r05hd_act_ab.txt)
+constexpr int PH_RING_DEPTH = 4;
 constexpr int PH_OBS_SHORT = 235, PH_CRITIC = 219, PH_Y1 = 14 * 32;
 constexpr int PH_NLAYER = 15;
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_ELU = 2 };
@@ -221,62 +207,12 @@ __global__ __launch_bounds__(256) void k_heads_pack(PhParams P, h8* __restrict__
 }
 
 // ---- the forward kernel
-typedef h8 Frag[2][64];  // one k-step of B fragments in LDS: [hi, lo][lane]
-
-struct ActorLds {
-  Frag x[20];  // actor input: short history (steps 0..14), estimate (15), history code (16..19)
-  Frag p[32];  // 512-wide activations (and the staged conv1 output, 28 steps)
-  Frag q[16];  // 256-wide activations
-};
-struct CriticLds {
-  Frag p[48];  // 768-wide activations
-  Frag q[16];  // the staged privileged observations (14 steps), then 256-wide activations
-};
-// split-K on the narrow layers (8 waves): a layer of NT < 8 output tiles deals each tile's k-steps over SK waves
-// (NT SK <= 8, at least two k-steps each, SK a power of two); waves kh = 1 .. SK-1 leave their partial 32 x 32 sums
-// (hi.hi + 2^-11 (hi.lo + lo.hi), one fp32 per element) in LDS and wave kh = 0 adds them in kh order before the bias
-// and the activation.  Measured +-0 (act() 0.1276-0.1292 ms off, 0.1282-0.1298 on, profiles/r07c_act_ab.txt): the
-// waves' k chains are not what bounds the kernel, its fragment stream from L2 is, so it stays off (A/B).
-#ifndef T1_HEADS_SPLITK
-#define T1_HEADS_SPLITK 0
-#endif
-constexpr int PH_RED_TILES = 4;  // partial tiles in LDS at once: (SK - 1) NT <= 4
-constexpr int ph_sk(int l) {
-  if (!T1_HEADS_SPLITK || PH_WAVES != 8) return 1;
-  const int nt = ph_nt(l), ks = PH_L[l].ks;
-  int sk = 1;
-  while (nt * sk * 2 <= PH_WAVES && ks % (sk * 2) == 0 && ks / (sk * 2) >= 2 && (sk * 2 - 1) * nt <= PH_RED_TILES)
-    sk *= 2;
-  return sk;
-}
-struct PhLds {
-  union {
-    ActorLds a;
-    CriticLds c;
-  };
-#if T1_HEADS_SPLITK
-  float4 red[PH_RED_TILES][4][64];  // split-K partial sums: [(kh - 1) NT + tile][register quad][lane]
-#endif
-};
-
-#ifndef T1_HEADS_FAST_ELU
-#define T1_HEADS_FAST_ELU 1  // act() 0.1336 -> 0.1279 ms at 8192 envs (profiles/r07b_act_ab.txt)
-#endif
-// expm1(v) for ELU's negative branch, branch-free.  1: the device library's expm1f algorithm (range reduction by
+// expm1(v) for ELU's negative branch, branch-free: the device library's expm1f algorithm (range reduction by
 // n = rint(v log2 e) with ln 2 in two parts, the same degree-7 polynomial, 2^n expm1(r) + (2^n - 1)) without its
 // overflow and v < -17 fix-ups, which v <= 0 never needs once v is clamped at -88: bit-identical to expm1f there (NaN
-// included).
-// 2: 2^(v log2 e) - 1 on the hardware exponential below -1/4, a degree-6 Taylor polynomial above (not bit-identical).
+// included).  act() 0.1336 -> 0.1279 ms at 8192 envs against expm1f under a branch; a hardware-exp2 form that is not
+// bit-identical measured the same, 0.1277 (profiles/r07b_act_ab.txt)
 __device__ __forceinline__ float ph_expm1_neg(float v) {
-#if T1_HEADS_FAST_ELU == 2
-  const float e = __builtin_amdgcn_exp2f(v * 1.44269504088896341f) - 1.0f;
-  float p = fmaf(v, 1.0f / 720.0f, 1.0f / 120.0f);
-  p = fmaf(v, p, 1.0f / 24.0f);
-  p = fmaf(v, p, 1.0f / 6.0f);
-  p = fmaf(v, p, 0.5f);
-  p = fmaf(v * v, p, v);
-  return v < -0.25f ? e : p;
-#else
   v = v < -88.0f ? -88.0f : v;  // (not fmaxf: a NaN stays a NaN, as in expm1f and torch's ELU)
   const float n = __builtin_rintf(v * __builtin_bit_cast(float, 0x3fb8aa3bu));
   float r = fmaf(n, __builtin_bit_cast(float, 0xbf317218u), v);
@@ -290,347 +226,45 @@ __device__ __forceinline__ float ph_expm1_neg(float v) {
   const float m = fmaf(r, p, r);  // expm1(r)
   const float t = __builtin_ldexpf(1.0f, (int)n);
   return fmaf(t, m, t - 1.0f);
-#endif
 }
 
 __device__ __forceinline__ float ph_act(float v, int act) {
   if (act == ACT_RELU) return v > 0.0f ? v : 0.0f;
-#ifdef T1_HEADS_WHATIF_NOELU  // timing-only what-if build: ELU as ReLU
-  if (act == ACT_ELU) return v > 0.0f ? v : 0.0f;
-#else
-#if T1_HEADS_FAST_ELU && defined(T1_HEADS_ELU_BRANCH)  // A/B: the expm1 under a branch per value (hipcc's choice)
-  if (act == ACT_ELU) return v > 0.0f ? v : ph_expm1_neg(v);
-#elif T1_HEADS_FAST_ELU
   if (act == ACT_ELU) {  // branch-free: expm1 of min(v, 0) (a NaN passes through), then the select
     const float e = ph_expm1_neg(v > 0.0f ? 0.0f : v);
     return v > 0.0f ? v : e;
   }
-#else
-  if (act == ACT_ELU) return v > 0.0f ? v : expm1f(v);
-#endif
-#endif
   return v;
-}
-
-// stage `steps` k-steps of natural-order B fragments from rows of global memory: element j of lane (r, h) of step s
-// = src[env r][col0 + 16 s + 8 h + j] (0 past len or past the batch), split into hi / lo.  Steps round-robin over the
-// waves.
-template <bool RELU>
-__device__ __forceinline__ void ph_stage(Frag* dst, int steps, const float* __restrict__ src, long long stride,
-                                         int col0, int len, int env, bool live, int wave, int lane) {
-  const int h = lane >> 5;
-  const float* row = src + (long long)env * stride + col0;
-  for (int s = wave; s < steps; s += PH_WAVES) {
-    float v[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int c = 16 * s + 8 * h + j;
-      // (non-temporal loads here, so the once-read inputs would not evict fragments: act() 0.129 -> 0.153 ms, r07c)
-      float x = (live && c < len) ? row[c] : 0.0f;
-      v[j] = RELU ? (x > 0.0f ? x : 0.0f) : x;
-    }
-    h8 hi, lo;
-    split8(v, hi, lo);
-    dst[s][0][lane] = hi;
-    dst[s][1][lane] = lo;
-  }
 }
 
 enum { OUT_LDS = 0, OUT_LDS_HALF = 1, OUT_MEAN = 2, OUT_VALUE = 3, OUT_MEAN_ONLY = 4, OUT_LDS_HALF_EST = 5 };
 
-struct PhOut {  // the global outputs (OUT_MEAN / OUT_VALUE layers)
-  const float* eps;
-  const float* std;
-  float* mean;
-  float* actions;
-  float* sigma;
-  float* logp;
-  float* value;
-  int env;
-  bool live;
-};
-
-// one dense layer for this wave's output tiles nt = wave + PH_WAVES i: B fragments from `in` (LDS), A fragments streamed
-// from the packed buffer, result + bias through the activation into `out` (LDS, k-steps out0 + 2 nt + {0, 1}) or the
-// global outputs.  Waves past the layer's tile count skip the products and store nothing.
-// the weight-fragment register ring of layer L: its loads run D k-steps ahead of their MFMAs through D + 1 slots
-// (about 16 x 96 MFMA cycles of cover over an L2 hit under load); its first D steps are issued during the previous
-// layer (ph_prologue), so no layer starts on an empty pipeline
-template <int L> struct PhRing {
-  static constexpr int NT = ph_nt(L), KS = PH_L[L].ks, SK = ph_sk(L), KL = KS / SK;
-  static constexpr int T = SK > 1 ? 1 : (NT + PH_WAVES - 1) / PH_WAVES;
-  // the wave's output tile i and the first of its KL k-steps (idle waves: a valid tile, loaded and never used)
-  static __device__ __forceinline__ int tile(int wave, int i) {
-    if constexpr (SK > 1) return wave % NT;
-    return (wave + PH_WAVES * i) < NT ? wave + PH_WAVES * i : NT - 1;
-  }
-  static __device__ __forceinline__ int kpart(int wave) { return SK > 1 && wave < NT * SK ? wave / NT : 0; }
-  static __device__ __forceinline__ bool busy(int wave) { return PH_WAVES == 4 || wave < NT * SK; }
-  // two waves per SIMD (PH_WAVES 8): the other wave covers part of the latency, and 256 VGPRs hold the accumulators
-  // and a ring of 1-4 steps (4 waves: 512 registers, 4-16 steps)
-  static constexpr int D0 = PH_WAVES == 8 ? (T >= 3 ? T1_HEADS_D3 : (T >= 2 ? T1_HEADS_D2 : T1_HEADS_D1))
-                                          : (T >= 4 ? 4 : (T >= 2 ? 8 : 16));
-  static constexpr int D = D0 < KL ? D0 : KL - 1;
-  static constexpr int R = D + 1;
-  h8 w[R][T][2];
-};
-template <int L>
-__device__ __forceinline__ void ph_load(const h8* __restrict__ frag, PhRing<L>& rg, int slot, int s, int wave,
-                                        int lane) {
-  typedef PhRing<L> G;
-  constexpr int OFF = ph_off(L);
-  const int ks = G::kpart(wave) * G::KL + s;  // s counts the wave's own k-steps
-#pragma unroll
-  for (int i = 0; i < G::T; ++i) {
-    const int nt = G::tile(wave, i);
-#ifdef T1_HEADS_WHATIF_NOLOAD  // timing-only what-if build: every fragment load hits the same 2 KB (L1)
-    const h8* w = frag + lane + (size_t)(((OFF + nt * G::KS + ks) & 0) * 2) * 64;
-#else
-    const h8* w = frag + lane + (size_t)((OFF + nt * G::KS + ks) * 2) * 64;
-#endif
-    rg.w[slot][i][0] = w[0];
-    rg.w[slot][i][1] = w[64];
-  }
-}
-template <int L>
-__device__ __forceinline__ void ph_prologue(const h8* __restrict__ frag, PhRing<L>& rg, int wave, int lane) {
-#pragma clang loop unroll(full)
-  for (int s = 0; s < PhRing<L>::D; ++s) ph_load<L>(frag, rg, s, s, wave, lane);
-}
-
-// one dense layer for this wave's output tiles nt = wave + PH_WAVES i: B fragments from `in` (LDS), A fragments through
-// the ring rg (prologue already issued), result + bias through the activation into `out` (LDS, k-steps
-// out0 + 2 nt + {0, 1}) or the global outputs.  LN >= 0: layer LN's prologue is issued into *nx before this layer's
-// epilogue.  Waves past the layer's tile count (8 waves, layers of < 8 tiles) skip the products and store nothing;
-// at 4 waves every layer has a tile per wave except the narrow heads, whose spare waves recompute the last tile.
-template <int L, int OUT, int LN>
-__device__ __forceinline__ void ph_layer(const h8* __restrict__ frag, const PhParams& P, const Frag* in, Frag* out,
-                                         int out0, const PhOut& G, int wave, int lane, PhRing<L>& rg,
-                                         PhRing<(LN < 0 ? L : LN)>* nx, float4 (*red)[4][64]) {
-  constexpr Layer Y = PH_L[L];
-  typedef PhRing<L> RG;
-  constexpr int NT = RG::NT, KL = RG::KL, SK = RG::SK, T = RG::T, D = RG::D, R = RG::R;
-  const int h = lane >> 5;
-  const int k0 = RG::kpart(wave) * KL;  // the wave's first k-step (split-K), wave-uniform
-  f16v acc0[T], acc1[T];
-#pragma unroll
-  for (int i = 0; i < T; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc0[i][r] = acc1[i][r] = 0.0f;
-  float4 bias[T][4];
-  h8 bq[2][2];
-  bq[0][0] = in[k0][0][lane];
-  bq[0][1] = in[k0][1][lane];
-  // a wave past the layer's tiles x k parts (PH_WAVES 8 on the narrow layers) skips the K loop (it stores nothing)
-  if (RG::busy(wave))
-#pragma clang loop unroll(full)
-  for (int s = 0; s < KL; ++s) {
-    if (s + D < KL) ph_load<L>(frag, rg, (s + D) % R, s + D, wave, lane);
-    if (s == KL - 1 - D) {  // the bias fragments behind the layer's last weight loads (no drain at the epilogue)
-      const float4* bf = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(frag) + PH_WFRAG_BYTES);
-#pragma unroll
-      for (int i = 0; i < T; ++i) {
-        const int nt = RG::tile(wave, i);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) bias[i][q] = bf[((ph_toff(L) + nt) * 4 + q) * 64 + lane];
-      }
-    }
-    if (s + 1 < KL) {
-      bq[(s + 1) & 1][0] = in[k0 + s + 1][0][lane];
-      bq[(s + 1) & 1][1] = in[k0 + s + 1][1][lane];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    const h8 bh = bq[s & 1][0], bl = bq[s & 1][1];
-#pragma unroll
-    for (int i = 0; i < T; ++i) {
-      const h8 ah = rg.w[s % R][i][0], al = rg.w[s % R][i][1];
-#ifdef T1_HEADS_WHATIF_NOMFMA  // timing-only what-if build: one MFMA per step-tile instead of three
-      acc0[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah + al, bh + bl, acc0[i], 0, 0, 0);
-#else
-      acc0[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc0[i], 0, 0, 0);
-      acc1[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc1[i], 0, 0, 0);
-      acc1[i] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc1[i], 0, 0, 0);
-#endif
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  if constexpr (LN >= 0) ph_prologue<LN>(frag, *nx, wave, lane);  // the next layer's first fragments in flight
-  float y[T][16];  // hi.hi + 2^-11 (hi.lo + lo.hi) per element, then the split-K partials in k order
-#pragma unroll
-  for (int i = 0; i < T; ++i)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) y[i][r] = acc0[i][r] + acc1[i][r] * (1.0f / PH_SPLIT);
-  if constexpr (SK > 1) {
-    const int kh = RG::kpart(wave);
-    if (RG::busy(wave) && kh > 0) {
-      float4(*dst)[64] = red[(kh - 1) * NT + wave % NT];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) dst[q][lane] = make_float4(y[0][4 * q], y[0][4 * q + 1], y[0][4 * q + 2], y[0][4 * q + 3]);
-    }
-    __syncthreads();  // every wave: the partials in LDS
-    if (wave < NT) {
-#pragma unroll
-      for (int p = 1; p < SK; ++p) {
-        const float4(*src)[64] = red[(p - 1) * NT + wave];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float4 u = src[q][lane];
-          y[0][4 * q] += u.x; y[0][4 * q + 1] += u.y; y[0][4 * q + 2] += u.z; y[0][4 * q + 3] += u.w;
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < T; ++i) {
-    const int nt = wave + PH_WAVES * i;
-    if (nt >= NT) break;  // wave-uniform (split-K: the kh = 0 waves, 0 .. NT - 1)
-    float v[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const float4 b4 = bias[i][r >> 2];
-      const float b = (r & 3) == 0 ? b4.x : (r & 3) == 1 ? b4.y : (r & 3) == 2 ? b4.z : b4.w;
-      v[r] = ph_act(y[i][r] + b, Y.act);
-    }
-    if constexpr (OUT == OUT_LDS || OUT == OUT_LDS_HALF) {
-#pragma unroll
-      for (int s = 0; s < (OUT == OUT_LDS ? 2 : 1); ++s) {
-        float u[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) u[j] = v[8 * s + j];
-        h8 hi, lo;
-        split8(u, hi, lo);
-        out[out0 + 2 * nt + s][0][lane] = hi;
-        out[out0 + 2 * nt + s][1][lane] = lo;
-      }
-    } else if constexpr (OUT == OUT_MEAN) {
-      // the Normal sample a = mean + sigma eps and its log-prob, summed over the 12 actions (DHPPO._act_body;
-      // torch.distributions.Normal.log_prob): rows 0-3, 8-11 on lane half 0, rows 4-7 on half 1
-      float lp = 0.0f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (row < Y.n && G.live) {
-          const float sd = G.std[row];
-          const size_t ix = (size_t)G.env * Y.n + row;
-          const float a = v[r] + sd * G.eps[ix];
-          const float d = a - v[r];
-          lp += -(d * d) / (2.0f * (sd * sd)) - logf(sd) - 0.91893853320467274178f;  // log(sqrt(2 pi))
-          G.mean[ix] = v[r];
-          G.actions[ix] = a;
-          G.sigma[ix] = sd;
-        }
-      }
-      lp += __shfl_xor(lp, 32);
-      if (h == 0 && G.live) G.logp[G.env] = lp;
-    } else {
-      if (h == 0 && G.live) G.value[G.env] = v[0];
-    }
-  }
-}
-
-__global__ __launch_bounds__(64 * PH_WAVES) __attribute__((amdgpu_waves_per_eu(PH_WAVES / 4, PH_WAVES / 4)))
-void k_heads(PhParams P, const h8* __restrict__ frag, const float* __restrict__ y1, const float* __restrict__ obs,
-             int obs_cols, const float* __restrict__ cobs, int cobs_cols, PhOut G, int batch, int xcd_split) {
-  __shared__ PhLds S;
-#if T1_HEADS_SPLITK
-  float4(*red)[4][64] = S.red;
-#else
-  float4(*red)[4][64] = nullptr;
-#endif
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  // role and tile: blockIdx mod 8 is the XCD; actor tiles on XCDs 0-3, critic tiles on 4-7 (xcd_split), else
-  // alternating
-  const int bid = blockIdx.x;
-  // xcd_split 2: both roles on every XCD, alternating in each XCD's dispatch order (a CU's two workgroups tend to be
-  // one actor chain and one critic; each L2 then holds both roles' 3.6 MB of fragments)
-  const bool critic = xcd_split == 2 ? ((bid >> 3) & 1) != 0 : (xcd_split ? (bid & 4) != 0 : (bid & 1) != 0);
-  const int tile = xcd_split == 2 ? ((bid >> 4) << 3) + (bid & 7) : (xcd_split ? (bid >> 3) * 4 + (bid & 3) : bid >> 1);
-  const int env0 = tile * PH_M;
-  if (env0 >= batch) return;
-  const int env = env0 + (lane & 31);
-  const bool live = env < batch;
-  const int envc = live ? env : batch - 1;
-  G.env = envc;
-  G.live = live;
-  if (!critic) {
-    ActorLds& A = S.a;
-    ph_stage<true>(A.p, 28, y1, PH_Y1, 0, PH_Y1, envc, live, wave, lane);                       // relu(conv1)
-    ph_stage<false>(A.x, 15, obs, obs_cols, obs_cols - PH_OBS_SHORT, PH_OBS_SHORT, envc, live, wave, lane);
-    PhRing<0> g0;
-    ph_prologue<0>(frag, g0, wave, lane);  // the first layer's fragments load across the barrier
-    __syncthreads();
-    PhRing<1> g1;
-    ph_layer<0, OUT_LDS, 1>(frag, P, A.p, A.q, 0, G, wave, lane, g0, &g1, red);
-    __syncthreads();
-    PhRing<2> g2;
-    ph_layer<1, OUT_LDS, 2>(frag, P, A.q, A.p, 0, G, wave, lane, g1, &g2, red);
-    __syncthreads();
-    PhRing<3> g3;
-    ph_layer<2, OUT_LDS, 3>(frag, P, A.p, A.x, 16, G, wave, lane, g2, &g3, red);  // history code -> actor input 16..19
-    PhRing<4> g4;
-    ph_layer<3, OUT_LDS, 4>(frag, P, A.x, A.q, 0, G, wave, lane, g3, &g4, red);  // reads steps 0..14 only: no barrier
-    __syncthreads();
-    PhRing<5> g5;
-    ph_layer<4, OUT_LDS, 5>(frag, P, A.q, A.p, 0, G, wave, lane, g4, &g5, red);
-    __syncthreads();
-    PhRing<6> g6;
-    ph_layer<5, OUT_LDS, 6>(frag, P, A.p, A.q, 0, G, wave, lane, g5, &g6, red);
-    __syncthreads();
-    PhRing<7> g7;
-    ph_layer<6, OUT_LDS_HALF, 7>(frag, P, A.q, A.x, 15, G, wave, lane, g6, &g7, red);  // estimate -> actor input 15
-    __syncthreads();
-    PhRing<8> g8;
-    ph_layer<7, OUT_LDS, 8>(frag, P, A.x, A.p, 0, G, wave, lane, g7, &g8, red);
-    __syncthreads();
-    PhRing<9> g9;
-    ph_layer<8, OUT_LDS, 9>(frag, P, A.p, A.q, 0, G, wave, lane, g8, &g9, red);
-    __syncthreads();
-    PhRing<10> g10;
-    ph_layer<9, OUT_LDS, 10>(frag, P, A.q, A.p, 0, G, wave, lane, g9, &g10, red);
-    __syncthreads();
-    ph_layer<10, OUT_MEAN, -1>(frag, P, A.p, nullptr, 0, G, wave, lane, g10, nullptr, red);
-  } else {
-    CriticLds& C = S.c;
-    ph_stage<false>(C.q, 14, cobs, cobs_cols, 0, PH_CRITIC, envc, live, wave, lane);
-    PhRing<11> g11;
-    ph_prologue<11>(frag, g11, wave, lane);
-    __syncthreads();
-    PhRing<12> g12;
-    ph_layer<11, OUT_LDS, 12>(frag, P, C.q, C.p, 0, G, wave, lane, g11, &g12, red);
-    __syncthreads();
-    PhRing<13> g13;
-    ph_layer<12, OUT_LDS, 13>(frag, P, C.p, C.q, 0, G, wave, lane, g12, &g13, red);
-    __syncthreads();
-    PhRing<14> g14;
-    ph_layer<13, OUT_LDS, 14>(frag, P, C.q, C.p, 0, G, wave, lane, g13, &g14, red);
-    __syncthreads();
-    ph_layer<14, OUT_VALUE, -1>(frag, P, C.p, nullptr, 0, G, wave, lane, g14, nullptr, red);
-  }
-}
-
-// ---- 64 envs per workgroup (k_heads64, the default; T1POLICY_HEADS64=0: the 32-env k_heads above, A/B).  At 32 envs
-// a workgroup takes ~42 us whether 256 or 512 of them run (4096 / 8192 envs, profiles/r07e), and its 139 KB of LDS
-// leaves one per CU, so 8192 envs take two rounds.  Here each weight fragment feeds BOTH 32-env column tiles (six
-// MFMAs per step-tile instead of three, the same fragment stream per workgroup), so 8192 envs take one round.  The LDS
-// holds 64 envs' activations in 144 KB because no layer output wider than 256 is ever resident: the actor's 512-wide
-// layer runs in two halves of 8 output tiles and the critic's 768-wide one in three, each half / third feeding the
-// next layer's accumulators (held in registers across the calls) before the next one overwrites it; the short
-// history is staged twice (the estimator's first layer, then the actor's).  Every layer call has one output tile per
-// wave (8 waves, T = 1).
-// ET: the 32-env column tiles of a workgroup.  2 = the 64-env workgroup above (act(), and the one-role inference
-// launches past one 32-env tile per CU); 1 = a 32-env workgroup with the same layer calls, k order and epilogues per env
-// column (the one-role inference launches up to one tile per CU: half the MFMAs per fragment, 72 KB of LDS).
+// ---- k_heads64: ET 32-env column tiles per workgroup.  A 32-env workgroup that keeps every layer's output in LDS
+// (139 KB, one per CU) takes ~42 us whether 256 or 512 of them run (4096 / 8192 envs, profiles/r07e), so 8192 envs took
+// two rounds.  With ET = 2 each weight fragment feeds BOTH column tiles (six MFMAs per step-tile instead of three, the
+// same fragment stream per workgroup), so 8192 envs take one round.  The LDS holds 64 envs' activations in 144 KB
+// because no layer output wider than 256 is ever resident: the actor's 512-wide layer runs in two halves of 8 output
+// tiles and the critic's 768-wide one in three, each half / third feeding the next layer's accumulators (held in
+// registers across the calls) before the next one overwrites it; the short history is staged twice (the estimator's
+// first layer, then the actor's).  Every layer call has one output tile per wave.
+// ET = 2: act(), and the one-role inference launches past one 32-env tile per CU.  ET = 1: a 32-env workgroup with the
+// same layer calls, k order and epilogues per env column (the one-role inference launches up to one tile per CU: half
+// the MFMAs per fragment, 72 KB of LDS).
+// Measured +-0 and not built: split-K over spare waves on the layers of fewer than 8 output tiles (act() 0.1276-0.1292
+// ms off, 0.1282-0.1298 on, profiles/r07c_act_ab.txt) -- the fragment stream from L2 bounds the kernel, not the waves'
+// k chains.
 template <int ET> using FragE = h8[ET][2][64];  // one k-step of B fragments of the ET env tiles: [env tile][hi, lo][lane]
 template <int ET> struct HeadsLds {
   FragE<ET> px[36];  // actor: PX[0..35]; critic: PX[0..31] (layout per phase in ph6_actor / ph6_critic)
 };
 
-// one layer call: layer L's output tiles [TB, TB + 8) (or to the layer's last tile) over its k-steps [KB, KE)
+// one layer call: layer L's output tiles [TB, TB + 8) (or to the layer's last tile) over its k-steps [KB, KE), and its
+// weight-fragment register ring: the loads run D k-steps ahead of their MFMAs through D + 1 slots; the first D are
+// issued during the previous call (ph6_prologue), so no call starts on an empty pipeline
 template <int L_, int KB_, int KE_, int TB_> struct P6Ring {
   static constexpr int L = L_, KB = KB_, KE = KE_, TB = TB_;
   static constexpr int NTL = ph_nt(L), TE = TB + PH_WAVES < NTL ? TB + PH_WAVES : NTL, NW = TE - TB;
-  static constexpr int KL = KE - KB, D = T1_HEADS_D1 < KL ? T1_HEADS_D1 : KL - 1, R = D + 1;
+  static constexpr int KL = KE - KB, D = PH_RING_DEPTH < KL ? PH_RING_DEPTH : KL - 1, R = D + 1;
   static_assert(PH_WAVES == 8 && KL >= 1 && NW >= 1 && KE <= PH_L[L].ks, "one output tile per wave");
   static __device__ __forceinline__ int tile(int wave) { return wave < NW ? TB + wave : TE - 1; }
   h8 w[R][2];
@@ -663,11 +297,14 @@ struct PhOut64 {  // the global outputs and the workgroup's envs
   int batch;
 };
 
-// staging as ph_stage, for both env tiles: element j of lane (r, h) of step s, tile et = src[env0 + 32 et + r][col0 +
-// 16 s + 8 h + j].  T: the source's element type.  An fp16 source (the env's fp16 histories) is its own hi part and its
-// lo part is exactly 0 -- what split8 makes of the widened value, so the staged fragments are the fp32 path's on
-// obs.float() bit for bit (finite values) -- read by 16-bit loads: its rows are 2-byte aligned only (an obs row's short
-// history starts at half 2867 of a 6204-byte row, a critic row is 438 B).
+// stage `steps` k-steps of natural-order B fragments from rows of global memory, for every env tile: element j of lane
+// (r, h) of step s, tile et = src[env0 + 32 et + r][col0 + 16 s + 8 h + j] (0 past len or past the batch), split into
+// hi / lo.  Steps round-robin over the waves.  (Non-temporal loads here, so that the once-read inputs would not evict
+// fragments: act() 0.129 -> 0.153 ms, profiles/r07c_act_ab.txt.)
+// T: the source's element type.  An fp16 source (the env's fp16 histories) is its own hi part and its lo part is
+// exactly 0 -- what split8 makes of the widened value, so the staged fragments are the fp32 path's on obs.float() bit
+// for bit (finite values) -- read by 16-bit loads: its rows are 2-byte aligned only (an obs row's short history starts
+// at half 2867 of a 6204-byte row, a critic row is 438 B).
 template <bool RELU, int ET, typename T>
 __device__ __forceinline__ void ph6_stage(FragE<ET>* dst, int steps, const T* __restrict__ src, long long stride,
                                           int col0, int len, int env0, int batch, int wave, int lane) {
@@ -795,7 +432,9 @@ __device__ __forceinline__ void ph6_call(const h8* __restrict__ frag, const Frag
           const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
           if (row < Y.n && live) G.mean[(size_t)env * Y.n + row] = v[r];
         }
-      } else if constexpr (OUT == OUT_MEAN) {  // as ph_layer's OUT_MEAN
+      } else if constexpr (OUT == OUT_MEAN) {
+        // the Normal sample a = mean + sigma eps and its log-prob, summed over the 12 actions (DHPPO._act_body;
+        // torch.distributions.Normal.log_prob): rows 0-3, 8-11 on lane half 0, rows 4-7 on half 1
         float lp = 0.0f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -931,7 +570,10 @@ void k_heads64(const h8* __restrict__ frag, const float* __restrict__ y1, const 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int bid = blockIdx.x;
-  // ROLE_BOTH: both roles on every XCD (blockIdx mod 8), alternating in each XCD's dispatch order (k_heads' xcd_split 2)
+  // ROLE_BOTH: both roles on every XCD (blockIdx mod 8), alternating in each XCD's dispatch order -- a CU's two
+  // workgroups tend to be one actor chain and one critic, and each L2 holds both roles' 3.6 MB of fragments: act()
+  // 0.139-0.140 ms, against 0.142 with the actor on XCDs 0-3 and the critic on 4-7 (the actor chain is 23% longer, so
+  // its XCDs finish last) and 0.140 with the roles alternating by workgroup (profiles/r05hx_act_ab.txt)
   const bool critic = ROLE == ROLE_BOTH ? ((bid >> 3) & 1) != 0 : ROLE == ROLE_CRITIC;
   const int tile = ROLE == ROLE_BOTH ? ((bid >> 4) << 3) + (bid & 7) : bid;
   G.env0 = tile * (32 * ET);
@@ -983,66 +625,6 @@ int t1policy_heads_pack(const uint64_t* params, const int* dims, void* frag, voi
   if (!ph_params(params, P)) return -1;
   hipLaunchKernelGGL(k_heads_pack, dim3(((PH_UNITS + PH_TILES) * 64 + 255) / 256), dim3(256), 0, (hipStream_t)stream, P,
                      reinterpret_cast<h8*>(frag));
-  return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-int t1policy_heads_forward(const uint64_t* params, const int* dims, const void* frag, const float* y1,
-                           const float* obs, int obs_cols, const float* critic_obs, int critic_cols, const float* eps,
-                           float* mean, float* actions, float* sigma, float* logp, float* value, int batch,
-                           void* stream) {
-  if (!params || !dims || !frag || !y1 || !obs || !critic_obs || !eps || !mean || !actions || !sigma || !logp ||
-      !value || batch < 0)
-    return -1;
-  if (!ph_dims_match(dims)) return 1;
-  if (obs_cols < PH_OBS_SHORT || critic_cols != PH_CRITIC) return 1;
-  if (batch == 0) return 0;
-  if ((reinterpret_cast<uintptr_t>(frag) & 15u) != 0) return -1;
-  PhParams P;
-  if (!ph_params(params, P)) return -1;
-  const char* hv = getenv("T1POLICY_HEADS64");  // 0: the 32-env k_heads (A/B)
-  if (!(hv && hv[0] == '0')) {
-    const PhOut64 G{eps, P.std, mean, actions, sigma, logp, value, nullptr, 0, batch};
-    const int tiles = (batch + 63) / 64;
-    hipLaunchKernelGGL(k_heads64<float>, dim3(16 * ((tiles + 7) / 8)), dim3(64 * PH_WAVES), 0, (hipStream_t)stream,
-                       reinterpret_cast<const h8*>(frag), y1, obs, obs_cols, critic_obs, critic_cols, G, batch);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-  }
-  PhOut G{eps, P.std, mean, actions, sigma, logp, value, 0, false};
-  const int tiles = (batch + PH_M - 1) / PH_M;
-  const char* xv = getenv("T1POLICY_HEADS_XCD");
-  // T1POLICY_HEADS_XCD (A/B): 2 (default) both roles alternating on every XCD, act() 0.139-0.140 ms; 1 actor on XCDs
-  // 0-3 / critic on 4-7, 0.142 (the actor chain is 23% longer, so the actor XCDs finish last); 0 alternating
-  // workgroups, 0.140 (profiles/r05hx_act_ab.txt)
-  const int xcd_split = xv && xv[0] == '0' ? 0 : (xv && xv[0] == '1' ? 1 : 2);
-  const int grid = xcd_split == 2 ? 16 * ((tiles + 7) / 8) : (xcd_split ? 8 * ((tiles + 3) / 4) : 2 * tiles);
-  hipLaunchKernelGGL(k_heads, dim3(grid), dim3(64 * PH_WAVES), 0, (hipStream_t)stream, P,
-                     reinterpret_cast<const h8*>(frag), y1, obs, obs_cols, critic_obs, critic_cols, G, batch,
-                     xcd_split);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-// heads_forward on fp16 obs / critic_obs: k_heads64<_Float16> (the 32-env k_heads has no fp16 instance: 1)
-int t1policy_heads_forward_h(const uint64_t* params, const int* dims, const void* frag, const float* y1,
-                             const void* obs, int obs_cols, const void* critic_obs, int critic_cols, const float* eps,
-                             float* mean, float* actions, float* sigma, float* logp, float* value, int batch,
-                             void* stream) {
-  if (!params || !dims || !frag || !y1 || !obs || !critic_obs || !eps || !mean || !actions || !sigma || !logp ||
-      !value || batch < 0)
-    return -1;
-  if (!ph_dims_match(dims)) return 1;
-  if (obs_cols < PH_OBS_SHORT || critic_cols != PH_CRITIC) return 1;
-  if (batch == 0) return 0;
-  if ((reinterpret_cast<uintptr_t>(frag) & 15u) != 0) return -1;
-  if (((reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(critic_obs)) & 1u) != 0) return -1;
-  PhParams P;
-  if (!ph_params(params, P)) return -1;
-  const char* hv = getenv("T1POLICY_HEADS64");
-  if (hv && hv[0] == '0') return 1;
-  const PhOut64 G{eps, P.std, mean, actions, sigma, logp, value, nullptr, 0, batch};
-  const int tiles = (batch + 63) / 64;
-  hipLaunchKernelGGL(k_heads64<_Float16>, dim3(16 * ((tiles + 7) / 8)), dim3(64 * PH_WAVES), 0, (hipStream_t)stream,
-                     reinterpret_cast<const h8*>(frag), y1, reinterpret_cast<const _Float16*>(obs), obs_cols,
-                     reinterpret_cast<const _Float16*>(critic_obs), critic_cols, G, batch);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -1114,10 +696,48 @@ int ph_critic_forward(const uint64_t* params, const int* dims, const void* frag,
                                           stream);
 }
 
+template <typename TO>
+int ph_heads_forward(const uint64_t* params, const int* dims, const void* frag, const float* y1, const TO* obs,
+                     int obs_cols, const TO* critic_obs, int critic_cols, const float* eps, float* mean,
+                     float* actions, float* sigma, float* logp, float* value, int batch, void* stream) {
+  if (!params || !dims || !frag || !y1 || !obs || !critic_obs || !eps || !mean || !actions || !sigma || !logp ||
+      !value || batch < 0)
+    return -1;
+  if (!ph_dims_match(dims)) return 1;
+  if (obs_cols < PH_OBS_SHORT || critic_cols != PH_CRITIC) return 1;
+  if (batch == 0) return 0;
+  if ((reinterpret_cast<uintptr_t>(frag) & 15u) != 0) return -1;
+  if (sizeof(TO) == 2 && ((reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(critic_obs)) & 1u) != 0)
+    return -1;
+  PhParams P;
+  if (!ph_params(params, P)) return -1;
+  const PhOut64 G{eps, P.std, mean, actions, sigma, logp, value, nullptr, 0, batch};
+  const int tiles = (batch + 63) / 64;
+  hipLaunchKernelGGL(k_heads64<TO>, dim3(16 * ((tiles + 7) / 8)), dim3(64 * PH_WAVES), 0, (hipStream_t)stream,
+                     reinterpret_cast<const h8*>(frag), y1, obs, obs_cols, critic_obs, critic_cols, G, batch);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 }  // namespace
 
 extern "C" {
 
+// act(): both roles in one launch, actor and critic tiles interleaved (k_heads64<.., 2, ROLE_BOTH>)
+int t1policy_heads_forward(const uint64_t* params, const int* dims, const void* frag, const float* y1,
+                           const float* obs, int obs_cols, const float* critic_obs, int critic_cols, const float* eps,
+                           float* mean, float* actions, float* sigma, float* logp, float* value, int batch,
+                           void* stream) {
+  return ph_heads_forward<float>(params, dims, frag, y1, obs, obs_cols, critic_obs, critic_cols, eps, mean, actions,
+                                 sigma, logp, value, batch, stream);
+}
+int t1policy_heads_forward_h(const uint64_t* params, const int* dims, const void* frag, const float* y1,
+                             const void* obs, int obs_cols, const void* critic_obs, int critic_cols, const float* eps,
+                             float* mean, float* actions, float* sigma, float* logp, float* value, int batch,
+                             void* stream) {
+  return ph_heads_forward<_Float16>(params, dims, frag, y1, reinterpret_cast<const _Float16*>(obs), obs_cols,
+                                    reinterpret_cast<const _Float16*>(critic_obs), critic_cols, eps, mean, actions,
+                                    sigma, logp, value, batch, stream);
+}
 // the deterministic policy and the estimate: the actor chain alone, every workgroup an actor tile (k_heads64<.., ROLE_ACTOR>)
 int t1policy_actor_forward(const uint64_t* params, const int* dims, const void* frag, const float* y1,
                            const float* obs, int obs_cols, float* mean, float* est_vel, int batch, void* stream) {
