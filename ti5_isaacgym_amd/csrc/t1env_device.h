@@ -471,11 +471,33 @@ __device__ __forceinline__ void zero_hist(float* buf, bool half, int64_t row, in
   }
 }
 
+// The same span zeroed 16 bytes per lane and store: the 16-byte-aligned middle of [o, o + count) with dwordx4 stores,
+// the elements ahead of and behind it one by one.  A row starts on a multiple of its width only (fp32 rows are 8-byte
+// aligned, fp16 rows 4-byte), and the span ends where the row's newest frame begins, which belongs to another wave: no
+// store reaches past either end.  A span without an aligned 16 bytes goes element by element.
+template <typename T>
+__device__ __forceinline__ void zero_span_wide(T* o, int count, int t0, int stride) {
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const uintptr_t a = reinterpret_cast<uintptr_t>(o), b = a + (uintptr_t)count * sizeof(T);
+  uintptr_t a16 = (a + 15) & ~(uintptr_t)15, b16 = b & ~(uintptr_t)15;
+  if (a16 > b16) a16 = b16 = b;
+  const int head = (int)((a16 - a) / sizeof(T)), mid = (int)((b16 - a16) / 16), tail = (int)((b - b16) / sizeof(T));
+  u32x4* const m = reinterpret_cast<u32x4*>(a16);
+  for (int c = t0; c < mid; c += stride) m[c] = u32x4{0u, 0u, 0u, 0u};
+  for (int c = t0; c < head; c += stride) o[c] = (T)0;
+  T* const t = reinterpret_cast<T*>(b16);
+  for (int c = t0; c < tail; c += stride) t[c] = (T)0;
+}
+__device__ __forceinline__ void zero_hist_wide(float* buf, bool half, int64_t row, int width, int count, int t0, int stride) {
+  if (half) zero_span_wide(reinterpret_cast<uint16_t*>(buf) + row * width, count, t0, stride);
+  else zero_span_wide(buf + row * width, count, t0, stride);
+}
+
 // reset_idx clears the obs / critic history deques of a reset env (t1_dh_stand_env.py:548-558): the 65 (2)
 // older frames of `row` in the freshly shifted output, lane t0 of `stride` lanes
 __device__ __forceinline__ void zero_history_row(const ShiftArgs& S, int64_t row, int t0, int stride) {
-  zero_hist(S.obs_out, S.half, row, T1_NOBS * T1_HIST, T1_NOBS * (T1_HIST - 1), t0, stride);
-  zero_hist(S.priv_out, S.half, row, T1_NPRIV * T1_CHIST, T1_NPRIV * (T1_CHIST - 1), t0, stride);
+  zero_hist_wide(S.obs_out, S.half, row, T1_NOBS * T1_HIST, T1_NOBS * (T1_HIST - 1), t0, stride);
+  zero_hist_wide(S.priv_out, S.half, row, T1_NPRIV * T1_CHIST, T1_NPRIV * (T1_CHIST - 1), t0, stride);
 }
 
 }  // namespace t1

@@ -28,7 +28,10 @@
 // -- slice s + 1's 16-B source load per output chunk is issued right after slice s's stores and held in
 // registers through the next substep's role work (ShiftHold), so the HBM stream spans the whole substep -- and stores
 // whole 16-B chunks (the newest frame of a row is a don't-care the epilogue rewrites; only the workgroup's last chunk
-// takes an element path).  The step's report and the fused epilogue are k_dyn5's, spread over the eight waves.
+// takes an element path).  The step's report and the fused epilogue are k_dyn5's, spread over the eight waves; the work
+// of an env's reset is kept off W0, whose reward pass and finaliser end the workgroup: W5-W7, which have no part in the
+// epilogue, zero the reset envs' history rows and lag rings, and W1 signals its terrain-level sum to W0 through a flag in
+// LDS (E2) and runs the rest of reset_idx behind it.
 //
 // Every value is computed by the same t1_dynamics.h / t1_dyn5.h functions as in k_dyn5; what differs is the order of a
 // few sums: a contact body's terms are the sum of its two point halves (and the self terms) instead of one 8-point
@@ -85,6 +88,16 @@ __device__ unsigned long long g_t1_wgsum6[4096][T1_WGSUM6_N];
 #define T1_CLOCK_WAVE_END()                                                        \
   if ((threadIdx.x & 63) == 0 && blockIdx.x < 4096)                                \
     atomicMax(&g_t1_wgtime6[blockIdx.x][2], (unsigned long long)__builtin_amdgcn_s_memrealtime());
+// and the tail of the last launch, per workgroup, in 100 MHz ticks (stamps into this buffer only).  W0 (the rewards
+// wave): [0] past the epilogue barrier, [1] post_a_core done, [2] its reset-row work issued, [3] its stores drained
+// (arrival at E2), [4] past E2, [5] the finaliser done.  W1 (the state wave): [8] past the epilogue barrier,
+// [9] post_a_core done, [10] its reset work ahead of E2 done, [11] the level sum stored and drained (arrival at E2),
+// [12] past E2, [13] its end
+constexpr int T1_TAIL6_N = 16;
+__device__ unsigned long long g_t1_tail6[4096][T1_TAIL6_N];
+#define T1_CLOCK_STAMP(k)                                                          \
+  if ((threadIdx.x & 63) == 0 && blockIdx.x < 4096)                                \
+    g_t1_tail6[blockIdx.x][k] = __builtin_amdgcn_s_memrealtime();
 #else
 #define T1_CLOCK_BEGIN() ((void)0)
 #define T1_CLOCK_END() ((void)0)
@@ -93,6 +106,7 @@ __device__ unsigned long long g_t1_wgsum6[4096][T1_WGSUM6_N];
 #define T1_CLOCK_WAIT_END(k) ((void)0)
 #define T1_CLOCK_SHIFT_END(wi) ((void)0)
 #define T1_CLOCK_LOOP_END() ((void)0)
+#define T1_CLOCK_STAMP(k) ((void)0)
 #endif
 
 #define T1_PROF_WAVES 8
@@ -147,6 +161,7 @@ struct Dyn6Lds {
   BaseParams<float> pb[64];  // registers held across the substep loop
   float rtf[2][3][64];    // the report: terrain forces on the shank [0] (W2) / foot [1] (W3)
   float rsf[2][3][64];    // the report: self-contact forces on the shank / foot (W5)
+  uint32_t e2;            // the epilogue's E2 flag: W1's terrain-level sum is stored (W1 -> W0)
 };
 T1_ROWS_ALIGNED(Dyn6Lds, st);
 T1_ROWS_ALIGNED(Dyn6Lds, wb);
@@ -973,15 +988,20 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
       }
     }
     if constexpr (FUSED) {
+      if (role == 1 && lane == 0) lds.e2 = 0u;
       __syncthreads();  // the epilogue barrier: every output of the workgroup is in LDS / memory
       T1_PROF_MARK(12);
       if (role == 1)
-        fused_epilogue_staged<POST_A_STATE, NE6, true>(M, C, B, A, S, FA, dyn_blocks, lane, lds.epi, lds.fr, lds.act,
-                                                       lds.act + NLEG);
+        fused_epilogue_staged<POST_A_STATE, NE6, true, /*RESET_ROWS=*/false>(M, C, B, A, S, FA, dyn_blocks, lane, lds.epi,
+                                                                             lds.fr, lds.act, lds.act + NLEG, &lds.e2);
       else if (role == 2)
         fused_epilogue_obs<POST_OBS_PRIV, NE6>(M, C, B, A, lane, lds.epi, lds.fr, lds.act, lds.act + NLEG);
       else if (role == 3)
         fused_epilogue_obs<POST_OBS_ACTOR, NE6>(M, C, B, A, lane, lds.epi, lds.fr, lds.act, lds.act + NLEG);
+      else if (wave >= 5)  // W5-W7 have no part in the epilogue: they zero the reset envs' history rows between them
+        // (not W4: the shift's arguments kept live to the end of its branch cost the <HF, FUSED> build two more
+        // spilled VGPRs)
+        epilogue_zero_reset_rows<NE6>(C, B, S, lane, (int)threadIdx.x - 320, 192, lds.epi, lds.fr);
       T1_PROF_MARK(15);
     }
     T1_CLOCK_WAVE_END();
@@ -1153,8 +1173,8 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
   if constexpr (FUSED) {
     __syncthreads();  // the epilogue barrier: every output of the workgroup is in LDS / memory
     T1_PROF_MARK(12);
-    fused_epilogue_staged<POST_A_REWARDS, NE6, true>(M, C, B, A, S, FA, dyn_blocks, lane, lds.epi, lds.fr, lds.act,
-                                                     lds.act + NLEG);
+    fused_epilogue_staged<POST_A_REWARDS, NE6, true, /*RESET_ROWS=*/false>(M, C, B, A, S, FA, dyn_blocks, lane, lds.epi,
+                                                                           lds.fr, lds.act, lds.act + NLEG, &lds.e2);
   }
   T1_CLOCK_END();
   T1_PROF_END();
@@ -1171,6 +1191,9 @@ extern "C" int t1env_debug_simd6(unsigned* out, int blocks) {
 // the read)
 extern "C" int t1env_debug_wgtime6(unsigned long long* out, int blocks) {
   return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_t1_wgtime6), sizeof(unsigned long long) * 4 * (size_t)blocks);
+}
+extern "C" int t1env_debug_tail6(unsigned long long* out, int blocks) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_t1_tail6), sizeof(unsigned long long) * T1_TAIL6_N * (size_t)blocks);
 }
 extern "C" int t1env_debug_wgsum6(unsigned long long* out, int blocks, int reset) {
   hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(g_t1_wgsum6), sizeof(unsigned long long) * T1_WGSUM6_N * (size_t)blocks);

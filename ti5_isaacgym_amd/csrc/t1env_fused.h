@@ -8,6 +8,11 @@
 #include "t1env_internal.h"
 #include "t1env_postphys.h"
 
+// tail stamps of a -DT1_PROBE_CLOCK build of k_dyn6 (t1env_dyn6.hip defines it ahead of this header); nothing elsewhere
+#ifndef T1_CLOCK_STAMP
+#define T1_CLOCK_STAMP(k) ((void)0)
+#endif
+
 namespace t1 {
 
 constexpr int SHIFT_UNIT = 8;  // rows per shift/zeroing unit (a multiple of 4: unit boundaries are 16-B aligned)
@@ -297,6 +302,50 @@ __device__ __forceinline__ void stage_epilogue_inputs(const t1env_buffers& B, in
   epi_stage_store<NE, NT>(N, nb, t, V, E);
 }
 
+// The same reset rows zeroed by waves that have no part in the epilogue (k_dyn6's W5-W7 once past the epilogue barrier),
+// so that the rewards wave, which carries the finaliser, stores none of them: thread t of nt (whole waves) takes its
+// share of every reset row.  Each wave forms the workgroup's reset mask itself from the LDS inputs, as the observation
+// waves do (check_termination on the same values as post_a_core: the base's contact force, the episode step).  The
+// shift's stores to these rows completed before the workgroup's R1 barrier (INWG).
+// They also zero the three lag rings of those envs (randomize_lag_props; 640 contiguous, 16-byte aligned bytes per env:
+// 160 one-lane stores of the state wave's reset_env_rest otherwise), which nothing reads before the kernel ends but the
+// actor wave's lagged samples, and those it drops for a resetting env.
+template <int NE>
+__device__ __forceinline__ void epilogue_zero_reset_rows(const t1env_config& C, const t1env_buffers& B,
+                                                         const ShiftArgs& S, int lane, int t, int nt,
+                                                         const float (*E)[NE], const float (*FR)[NE]) {
+  const int e = lane % NE;
+  const int n = (int)blockIdx.x * NE + lane;
+  const int64_t el = (int64_t)(((uint64_t)(uint32_t)__float_as_int(E[E_EL + 1][e]) << 32) |
+                               (uint32_t)__float_as_int(E[E_EL][e])) + 1;
+  const bool term = norm3(FR[F_CFB][e], FR[F_CFB + 1][e], FR[F_CFB + 2][e]) > 1.0f;
+  const bool tout = (float)el > C.max_episode_length;
+  unsigned long long todo = __ballot(lane < NE && n < C.num_envs && (term || tout));
+  while (todo) {
+    const int l = __ffsll(todo) - 1;
+    todo &= todo - 1;
+    const int64_t row = (int64_t)blockIdx.x * NE + l;
+    zero_history_row(S, row, t, nt);
+    zero_span_wide(B.act_hist + row * 48, 48, t, nt);
+    zero_span_wide(B.dof_hist + row * 96, 96, t, nt);
+    zero_span_wide(B.imu_hist + row * 16, 16, t, nt);
+  }
+}
+
+// The state wave's reset_idx past the terrain curriculum: the rest of the env's new state, its new gait times (the
+// reset's draws again) and the commands redrawn at the new episode's start
+__device__ __forceinline__ void epilogue_reset_rest(const DynModel& M, const t1env_config& C, const t1env_buffers& B,
+                                                    const t1env_step_args& A, int n, uint32_t genv, uint32_t ctr,
+                                                    RngKey K, const float (&cmd)[4], float org[3], bool org_known,
+                                                    bool zero_lag_rings) {
+  reset_env_rest(M, C, B, n, K, org, org_known, /*zero_reward_state=*/false, /*obs_elsewhere=*/true, zero_lag_rings);
+  ObsIn O;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) O.cmd[i] = cmd[i];
+  reset_obs_inputs(M, C, K, O, /*dof=*/false);
+  if (resample_commands_r(C, A, O.el, O.gt, O.cmd, genv, ctr)) strow(B.commands + n * 4, O.cmd);
+}
+
 // The fused step's post-physics for the NE envs of one workgroup, run by four waves after the epilogue barrier (lane =
 // env; lanes >= NE shadow an env of the workgroup and store nothing), every input from LDS (fresh outputs FR, staged
 // state E, the clipped actions in ACT0 (joints 0-5) / ACT1 (joints 6-11)).  This function is the two post_a waves:
@@ -304,13 +353,20 @@ __device__ __forceinline__ void stage_epilogue_inputs(const t1env_buffers& B, in
 // sums and the reset rows, POST_A_STATE the state stores, reset_idx of the resetting envs (their new state, commands
 // redrawn) and the terrain-level sum.  The observations are the other two waves' (fused_epilogue_obs).  After one
 // barrier the rewards wave signals completion (the extras finaliser).
-template <int PART, int NE, bool INWG>
+// RESET_ROWS = false (k_dyn6): the reset rows' zeroing and the lag rings' are left to waves outside the epilogue
+// (epilogue_zero_reset_rows).
+// e2_flag (k_dyn6, with RESET_ROWS = false): E2 is a flag in LDS instead of a barrier.  The state wave sets it once its
+// level sum is stored and goes on; the rewards wave waits for it alone.  The flag is 0 before the epilogue barrier.
+template <int PART, int NE, bool INWG, bool RESET_ROWS = true>
 __device__ __forceinline__ void fused_epilogue_staged(const DynModel& M, const t1env_config& C, const t1env_buffers& B,
                                                       const t1env_step_args& A, const ShiftArgs& S,
                                                       const FusedArgs& FA, int dyn_blocks, int lane,
                                                       const float (*E)[NE], const float (*FR)[NE],
-                                                      const float (*ACT0)[NE], const float (*ACT1)[NE]) {
+                                                      const float (*ACT0)[NE], const float (*ACT1)[NE],
+                                                      uint32_t* e2_flag = nullptr) {
   const int N = C.num_envs;
+  constexpr int TS = PART == POST_A_REWARDS ? 0 : 8;  // this wave's tail stamps (a probe build's)
+  T1_CLOCK_STAMP(TS);
   const int e = lane % NE;  // the LDS column (lanes >= NE read a valid column and are inactive)
   const int n0 = lane < NE ? (int)blockIdx.x * NE + lane : N;
   const bool active = n0 < N;
@@ -358,32 +414,60 @@ __device__ __forceinline__ void fused_epilogue_staged(const DynModel& M, const t
   X.gstart = E[E_GS][e];
   BaseQ bq;
   float* const ep_row = FA.ep_part + (size_t)blockIdx.x * EP_PART_ROW;  // this workgroup's partial extras sums
+  // the state wave's term of the terrain-level sum: the env's level as it stands, read ahead of post_a_core's stores
+  const bool in_level_sum = PART == POST_A_STATE && C.custom_origins && active;
+  int level = in_level_sum ? B.terrain_levels[n] : 0;
   const bool do_reset = post_a_core<PART>(M, C, B, A, n0, X, bq, PART == POST_A_REWARDS ? ep_row : nullptr);
   T1_PROF_MARK(13);
+  T1_CLOCK_STAMP(TS + 1);
   if constexpr (PART == POST_A_REWARDS) {
-    epilogue_handoff<NE, INWG>(C, S, FA, lane, do_reset, active);
+    if constexpr (RESET_ROWS) epilogue_handoff<NE, INWG>(C, S, FA, lane, do_reset, active);
+    T1_CLOCK_STAMP(TS + 2);
     __builtin_amdgcn_s_waitcnt(0);  // this wave's atomics (extras sums) complete
-    __syncthreads();                // E2: the state wave's terrain-level sum complete
+    T1_CLOCK_STAMP(TS + 3);
+    if (e2_flag) {  // E2: the state wave's terrain-level sum complete
+      while (__hip_atomic_load(e2_flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u) __builtin_amdgcn_s_sleep(1);
+    } else {
+      __syncthreads();
+    }
+    T1_CLOCK_STAMP(TS + 4);
     epilogue_finalize_parts(C, B, A, FA, dyn_blocks, lane);
+    T1_CLOCK_STAMP(TS + 5);
     T1_PROF_MARK(15);
     return;
   }
-  if (active && do_reset) {  // reset_idx (post_b's first half): the new state; the observation waves take its inputs
-    const uint32_t genv = (uint32_t)(C.env_offset + n);
-    const uint32_t ctr = A.counter + 1u;
+  // reset_idx (post_b's first half) of the resetting envs, in two parts: the terrain curriculum, which settles the
+  // terrain-level sum the rewards wave needs before it may enter the extras finaliser, and the rest of the new state
+  // (about 60 draws and 300 one-lane stores), the gait times and the redrawn commands, which nothing waits for but the
+  // end of the kernel.  With E2 as a flag the level sum is stored and signalled between the two and this wave never
+  // waits.  With E2 as a barrier the whole reset stays ahead of it: this wave would stand at the barrier until the
+  // rewards wave's longer pass arrives and only then run the rest (measured slower).  The
+  // observation waves take a resetting env's inputs from its draws, not from these rows.
+  const uint32_t genv = (uint32_t)(C.env_offset + n);
+  const uint32_t ctr = A.counter + 1u;
+  const RngKey K = rng_key(C.seed, genv, ctr);
+  float org[3];
+  bool org_known = false;
+  if (active && do_reset) {
     const float pos_cmd[4] = {X.root[0], X.root[1], X.cmd[0], X.cmd[1]};
-    reset_env(M, C, B, A, n, genv, ctr, true, /*zero_reward_state=*/false, /*obs_elsewhere=*/true, pos_cmd);
-    ObsIn O;  // the new gait times (the reset's draws again), then the commands redrawn at the new episode's start
-#pragma unroll
-    for (int i = 0; i < 4; ++i) O.cmd[i] = X.cmd[i];
-    reset_obs_inputs(M, C, rng_key(C.seed, genv, ctr), O, /*dof=*/false);
-    if (resample_commands_r(C, A, O.el, O.gt, O.cmd, genv, ctr)) strow(B.commands + n * 4, O.cmd);
+    org_known = reset_curriculum(C, B, n, K, true, pos_cmd, org, level, in_level_sum);
   }
+  if (!e2_flag && active && do_reset)
+    epilogue_reset_rest(M, C, B, A, n, genv, ctr, K, X.cmd, org, org_known, /*zero_lag_rings=*/RESET_ROWS);
   T1_PROF_MARK(14);
-  // the terrain-level sum reads the levels reset_idx may just have changed
-  wave_sum_store(ep_row + T1_ACC_LEVEL, (C.custom_origins && active) ? (float)B.terrain_levels[n] : 0.0f);
+  T1_CLOCK_STAMP(TS + 2);
+  wave_sum_store(ep_row + T1_ACC_LEVEL, in_level_sum ? (float)level : 0.0f);  // the levels after the curriculum
   __builtin_amdgcn_s_waitcnt(0);
-  __syncthreads();  // E2
+  T1_CLOCK_STAMP(TS + 3);
+  if (e2_flag) {  // E2
+    if (lane == 0) __hip_atomic_store(e2_flag, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+  } else {
+    __syncthreads();
+  }
+  T1_CLOCK_STAMP(TS + 4);
+  if (e2_flag && active && do_reset)
+    epilogue_reset_rest(M, C, B, A, n, genv, ctr, K, X.cmd, org, org_known, /*zero_lag_rings=*/RESET_ROWS);
+  T1_CLOCK_STAMP(TS + 5);
   T1_PROF_MARK(15);
 }
 

@@ -673,38 +673,47 @@ __device__ __forceinline__ void reset_obs_inputs(const DynModel& M, const t1env_
   X.pl = 0;
 }
 
+// reset_idx's first part, _update_terrain_curriculum (legged_robot.py:732-783): the env's new terrain level and origin,
+// stored (terrain_levels, env_origins) and returned in lv / org (lv_known: lv holds the env's level as it stands, so it
+// is not read again).  Returns whether it ran; if not, lv and org are left as they are.  The fused epilogue runs it alone ahead of its E2 barrier: the terrain-level sum the extras finaliser
+// waits for needs nothing else of the reset.
+// pos_cmd: the env's root position (x, y) and commands as they stand (the caller's registers) instead of memory
+__device__ __forceinline__ bool reset_curriculum(const t1env_config& C, const t1env_buffers& B, int n, RngKey K,
+                                                 bool do_terrain, const float* pos_cmd, float org[3], int& lv_io,
+                                                 bool lv_known = false) {
+  if (!(do_terrain && C.terrain_curriculum)) return false;
+  const float* r = pos_cmd ? pos_cmd : B.root_states + n * 13;
+  const float* o = B.env_origins + n * 3;
+  const float dist = norm2(r[0] - o[0], r[1] - o[1]);
+  const bool up = dist > C.env_length / 2.0f;
+  const float* cmd = pos_cmd ? pos_cmd + 2 : B.commands + n * 4;
+  const bool down = (dist < norm2(cmd[0], cmd[1]) * (C.episode_length_s * 0.5f)) && !up;
+  int lv = (lv_known ? lv_io : B.terrain_levels[n]) + (up ? 1 : 0) - (down ? 1 : 0);
+  const int rnd = rand_int(0, C.num_terrain_rows, K, SLOT_TERRAIN_LEVEL_RAND);
+  lv = lv >= C.num_terrain_rows ? rnd : (lv < 0 ? 0 : lv);
+  B.terrain_levels[n] = lv;
+  const float* to = B.terrain_origins + ((size_t)lv * C.num_terrain_cols + B.terrain_types[n]) * 3;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    org[i] = to[i];
+    B.env_origins[n * 3 + i] = org[i];
+  }
+  lv_io = lv;
+  return true;
+}
+
+// reset_idx's second part: everything but the terrain curriculum.  org: the env's origin if org_known (from
+// reset_curriculum), read from env_origins otherwise.
 // zero_reward_state = false: the caller's reward pass zeroes feet_air_time and the episode sums itself (the fused
 // epilogue, where that pass runs on another wave concurrently: post_a_core<POST_A_REWARDS>)
 // (the new state's observation inputs: reset_obs_inputs, from the same draws, instead of reading back the rows just
 // written -- one dependent memory round trip less)
 // obs_elsewhere: the last_* rows are left to the wave that writes the observations (the fused epilogue's post_b
 // stores them after the reset, with the values reset_obs_inputs gives; two waves storing one row would race)
-// pos_cmd: the env's root position (x, y) and commands as they stand (the caller's registers) instead of memory
-__device__ __forceinline__ void reset_env(const DynModel& M, const t1env_config& C, const t1env_buffers& B, const t1env_step_args& A,
-                          int n, uint32_t genv, uint32_t ctr, bool do_terrain, bool zero_reward_state = true,
-                          bool obs_elsewhere = false, const float* pos_cmd = nullptr) {
-  const RngKey K = rng_key(C.seed, genv, ctr);
-  float org[3];
-  bool org_known = false;
-  if (do_terrain && C.terrain_curriculum) {  // _update_terrain_curriculum
-    const float* r = pos_cmd ? pos_cmd : B.root_states + n * 13;
-    const float* o = B.env_origins + n * 3;
-    const float dist = norm2(r[0] - o[0], r[1] - o[1]);
-    const bool up = dist > C.env_length / 2.0f;
-    const float* cmd = pos_cmd ? pos_cmd + 2 : B.commands + n * 4;
-    const bool down = (dist < norm2(cmd[0], cmd[1]) * (C.episode_length_s * 0.5f)) && !up;
-    int lv = B.terrain_levels[n] + (up ? 1 : 0) - (down ? 1 : 0);
-    const int rnd = rand_int(0, C.num_terrain_rows, K, SLOT_TERRAIN_LEVEL_RAND);
-    lv = lv >= C.num_terrain_rows ? rnd : (lv < 0 ? 0 : lv);
-    B.terrain_levels[n] = lv;
-    const float* to = B.terrain_origins + ((size_t)lv * C.num_terrain_cols + B.terrain_types[n]) * 3;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      org[i] = to[i];
-      B.env_origins[n * 3 + i] = org[i];
-    }
-    org_known = true;
-  }
+__device__ __forceinline__ void reset_env_rest(const DynModel& M, const t1env_config& C, const t1env_buffers& B,
+                                               int n, RngKey K, float org[3], bool org_known,
+                                               bool zero_reward_state = true, bool obs_elsewhere = false,
+                                               bool zero_lag_rings = true) {
   if (!org_known)
 #pragma unroll
     for (int i = 0; i < 3; ++i) org[i] = B.env_origins[n * 3 + i];
@@ -742,12 +751,14 @@ __device__ __forceinline__ void reset_env(const DynModel& M, const t1env_config&
                                         SLOT_DR_ARMATURE + (C.armature_shared ? 0 : j));
   }
   // randomize_lag_props: zero the lag rings, redraw lag lengths
+  if (zero_lag_rings) {  // (false: the caller has other lanes zero them, zero_lag_rings_wide)
 #pragma unroll
-  for (int i = 0; i < 48; ++i) B.act_hist[(size_t)n * 48 + i] = 0.0f;
+    for (int i = 0; i < 48; ++i) B.act_hist[(size_t)n * 48 + i] = 0.0f;
 #pragma unroll
-  for (int i = 0; i < 96; ++i) B.dof_hist[(size_t)n * 96 + i] = 0.0f;
+    for (int i = 0; i < 96; ++i) B.dof_hist[(size_t)n * 96 + i] = 0.0f;
 #pragma unroll
-  for (int i = 0; i < 16; ++i) B.imu_hist[(size_t)n * 16 + i] = 0.0f;
+    for (int i = 0; i < 16; ++i) B.imu_hist[(size_t)n * 16 + i] = 0.0f;
+  }
   B.lag_timestep[n] = rand_int(C.lag_range[0], C.lag_range[1] + 1, K, SLOT_LAG_ACTION);
   B.dof_lag_timestep[n] = R.dl;
   B.imu_lag_timestep[n] = R.il;
@@ -779,6 +790,17 @@ __device__ __forceinline__ void reset_env(const DynModel& M, const t1env_config&
     for (int k = 0; k < T1_NREW; ++k) B.episode_sums[(size_t)k * C.num_envs + n] = 0.0f;
   // base quantities of the reset env from the fresh root state (t1:548-552)
   store_base_quantities(B, n, R.bq);
+}
+
+// reset_idx for one env, both parts back to back (the split kernels)
+__device__ __forceinline__ void reset_env(const DynModel& M, const t1env_config& C, const t1env_buffers& B, const t1env_step_args& A,
+                          int n, uint32_t genv, uint32_t ctr, bool do_terrain, bool zero_reward_state = true,
+                          bool obs_elsewhere = false, const float* pos_cmd = nullptr) {
+  const RngKey K = rng_key(C.seed, genv, ctr);
+  float org[3];
+  int lv;
+  const bool org_known = reset_curriculum(C, B, n, K, do_terrain, pos_cmd, org, lv);
+  reset_env_rest(M, C, B, n, K, org, org_known, zero_reward_state, obs_elsewhere);
 }
 
 // the actor-frame noise of observation i (legged_robot.py compute_observations: (2 u - 1) * noise_vec * level, u keyed

@@ -9,6 +9,11 @@ The per-workgroup sums split W0's S1 waits into the first S1 of the launch (W0 w
 prologue: the staging loads) and the S1s of substeps 1+ (it waits for the shift waves' S2 -> S1 tails: their stores and
 next loads), and give each shift role's S2 -> S1 tail by shift index (roles 1, 2, 3, 5, 6, 7).  The modes of a build
 are per process: run it in several fresh processes.
+
+`tail_by_resets` splits the time of W0 (the rewards wave, which carries the finaliser) and W1 (the state wave, which
+carries reset_idx) past the epilogue barrier at the build's tail stamps -- W0: post_a_core, its reset-row work, its
+store drain, the wait at E2, the finaliser; W1: post_a_core, its reset work ahead of E2, the level sum, the wait at E2,
+what it runs behind E2 -- by the workgroup's reset count that step, over --samples further launches.
 """
 import argparse
 import ctypes
@@ -27,10 +32,45 @@ from ti5_isaacgym_amd import make_t1_env  # noqa: E402
 NSUM = 10  # T1_WGSUM6_N: W0 life, S1 waits of substeps 1+, S2 waits, first S1 wait, six shift roles' S2 -> S1 tails
 
 
+# the tail stamps of a workgroup (T1_TAIL6_N = 16 ticks of 100 MHz, t1env_dyn6.hip): W0 at 0-5, W1 at 8-13
+TAIL_SEGMENTS = {"w0_post_a_core": (0, 1), "w0_reset_rows": (1, 2), "w0_store_drain": (2, 3), "w0_e2_wait": (3, 4),
+                 "w0_finaliser": (4, 5), "w1_post_a_core": (8, 9), "w1_reset_before_e2": (9, 10),
+                 "w1_level_sum_and_drain": (10, 11), "w1_e2_wait": (11, 12), "w1_after_e2": (12, 13),
+                 "w0_barrier_to_end": (0, 5), "w1_barrier_to_e2": (8, 11)}
+
+
+def tail_by_resets(lib, env, acts, wg, samples):
+    """The time of W0 and W1 past the epilogue barrier, split at the tail stamps, over `samples` further launches (each
+    synchronised and read back): the mean of every segment in workgroups without a reset, with one, and with more; W0's
+    loop-end-to-last-instruction time likewise; and how many of each launch's six last-finishing workgroups hold a reset."""
+    seg = {k: {"0": [], "1": [], ">=2": []} for k in list(TAIL_SEGMENTS) + ["epilogue"]}
+    last6, wgs = [], []
+    tl, tail = np.zeros((wg, 4), np.uint64), np.zeros((wg, 16), np.uint64)
+    for i in range(samples):
+        env.step(acts[i % 8])
+        torch.cuda.synchronize()
+        lib.t1env_debug_wgtime6(tl.ctypes.data_as(ctypes.c_void_p), wg)
+        lib.t1env_debug_tail6(tail.ctypes.data_as(ctypes.c_void_p), wg)
+        rs = env.reset_buf.detach().to(torch.int32).cpu().numpy()[: wg * 32].reshape(wg, 32).sum(1)
+        t, w = tail.astype(np.int64) / 100.0, tl.astype(np.int64) / 100.0
+        groups = {"0": rs == 0, "1": rs == 1, ">=2": rs >= 2}
+        for k, (i0, i1) in TAIL_SEGMENTS.items():
+            for g, m in groups.items():
+                seg[k][g].extend((t[m, i1] - t[m, i0]).tolist())
+        for g, m in groups.items():
+            seg["epilogue"][g].extend((w[m, 1] - w[m, 3]).tolist())
+        last6.append(int((rs[np.argsort(-w[:, 2])[:6]] > 0).sum()))
+        wgs.append(int((rs > 0).sum()))
+    mean = lambda v: round(float(np.mean(v)), 2) if v else None  # noqa: E731
+    return {"us_mean": {k: {g: mean(v) for g, v in d.items()} for k, d in seg.items()}, "launches": samples,
+            "reset_wgs_per_launch_mean": mean(wgs), "reset_wgs_among_last_six_finishers": last6}
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument("--steps", type=int, default=300)
     p.add_argument("--num-envs", type=int, default=8192)
+    p.add_argument("--samples", type=int, default=16, help="launches sampled for the tail split (tail_by_resets)")
     p.add_argument("--dump", default=None, help="save the per-workgroup (life, S1 wait, S2 wait) us array (.npy)")
     a = p.parse_args()
     N = a.num_envs
@@ -76,7 +116,8 @@ def main():
                      ">=1": round(float(epi_t[rs > 0].mean()), 2) if (rs > 0).any() else None,
                      "wgs_with_resets": int((rs > 0).sum())}
     q = lambda v: [round(float(x), 2) for x in np.quantile(v, [0, 0.5, 0.9, 1.0])]  # noqa: E731
-    print(json.dumps({"ms_per_step": round(ms, 4), "launches_x_workgroups": launches,
+    tail = tail_by_resets(lib, env, acts, wg, a.samples) if hasattr(lib, "t1env_debug_tail6") else None
+    print(json.dumps({"tail_by_resets": tail,"ms_per_step": round(ms, 4), "launches_x_workgroups": launches,
                       "shader_mhz": round(mhz, 1) if mhz else None,
                       "w0_lifetime_us_mean": round(ticks / max(1, launches) / 100.0, 2),
                       "last_launch_us": {"start_q0_50_90_100": q(st), "w0_life_q": q(w0e - st),
