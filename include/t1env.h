@@ -270,9 +270,12 @@ int t1env_reset_idx(t1env* env, const uint8_t* mask, const t1env_step_args* args
  * need the host to read ep_accum between the phases, so the step is exposed in two halves:
  *   t1env_step_physics_and_rewards  -> physics, post_a (callback, termination, rewards, extras reduction)
  *   t1env_step_reset_and_observe    -> post_b (reset_idx of flagged envs, observations, newest history frame)
- * The 65 older history frames are shifted by extra workgroups of phase A's dynamics launch (it reads only the
- * previous step's buffer, so it overlaps the dynamics on the CUs they leave idle); post_b follows in stream
- * order.  Everything runs on the caller's stream: no internal streams or events.
+ * The 65 older history frames are shifted during phase A: inside the step kernel (k_dyn6, k_dyn5), or by a shift
+ * launch on the env's own side stream beside it (k_dyn4; k_dyn5 with T1ENV_D5_SHIFT=1), forked from the caller's
+ * stream before the step kernel and joined to it after (it reads only the previous step's buffer, so it overlaps
+ * the dynamics); post_b follows in stream order.  Work the caller enqueues after a call is ordered after all of it.
+ * t1env_step_reset_and_observe without a preceding phase A (and t1env_step_injected) runs the shift launch first,
+ * in order on the caller's stream.
  * t1env_step() runs both back to back (no host sync). */
 int t1env_step(t1env* env, const float* actions, const t1env_step_args* args, void* stream);
 int t1env_step_physics_and_rewards(t1env* env, const float* actions, const t1env_step_args* args, void* stream);
@@ -293,14 +296,15 @@ int t1env_measure_heights(t1env* env, const float* points, int32_t npts, float* 
 int t1env_critic_heights(t1env* env, int32_t obs_slot, int32_t npts, float scale, const float* measured,
                          const float* prev, float* out, void* stream);
 /* t1env_step runs the whole step as ONE launch by default (fused): the history shift and post-physics ride in
- * the dynamics kernel (post-physics in its epilogue).  enable = 0 makes t1env_step run the split sequence
+ * the step kernel (post-physics in its epilogue; with k_dyn4 the shift is the side launch beside it).  enable = 0 makes t1env_step run the split sequence
  * (physics_and_rewards + reset_and_observe) instead; both give the same buffers.  The split entry points are
  * unaffected (they are what command-curriculum steps use). */
 int t1env_set_fused(t1env* env, int32_t enable);
 int t1env_set_substep_log(t1env* env, const t1env_substep_log* log);
 /* Per-kernel timing with HIP events recorded around every launch (bench.py's live roofline).  Ids:
- * 0 k_dynamics incl. its history-shift workgroups (or the injected-physics kernel), 1 k_post_a, 2 k_post_b (its
- * last block also finalises the extras), 3 stand-alone k_shift (injected physics or phase B without phase A),
+ * 0 the step kernel incl. an in-kernel history shift (or the injected-physics kernel), 1 k_post_a, 2 k_post_b (its
+ * last block also finalises the extras), 3 the history shift as its own launch (beside k_dyn4 / k_dyn5 on the side
+ * stream, or in stream order for injected physics and phase B without phase A),
  * 4 unused, 5 the whole step (phase A start .. phase B end).  get_timing synchronises and returns summed milliseconds and launch counts per id since
  * the last enable. */
 #define T1ENV_NTIMERS 6

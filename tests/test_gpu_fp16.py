@@ -9,8 +9,8 @@ seed and stepped with the same actions must agree:
     shifted and the reset-zeroed ones);  |fp16 - fp32| <= 2**-11 |fp32| follows (half an fp16 ulp, relative);
   * rewards, resets, root / dof state and every other buffer: bit-identical (same kernels, same inputs).
 
-Run at configs[4]'s size (32768 envs, height field, pushes; the history shift is its own launch there) and on a
-ragged 777-env trimesh run (fused shift workgroups, partial last unit), each for 12 steps with resets.
+Run at configs[4]'s size (32768 envs, height field, pushes; k_dyn4 beside the k_shift4c side launch there) and on a
+ragged 777-env trimesh run (the step kernel's own shift, partial last unit), each for 12 steps with resets.
 """
 import pytest
 import torch

@@ -1,7 +1,7 @@
-"""Full HIP step path (k_dynamics + its history-shift workgroups, k_post_a, k_post_b) at BASELINE sizes.
+"""Full HIP step path (the step kernel with its history shift, k_post_a, k_post_b) at BASELINE sizes.
 
 The golden fixtures pin post-physics on injected states at small N (test_gpu_parity.py).  Here the product
-path runs as bench.py runs it -- real dynamics, the history shift fused into the dynamics launch -- at the
+path runs as bench.py runs it -- real dynamics, the history shift inside or beside the step kernel -- at the
 BASELINE configs, checked through properties that hold at any size:
 
   * history: for envs not reset this step, the 66-frame obs and 3-frame critic histories are the previous

@@ -1,15 +1,17 @@
 // t1env.hip -- MI355X (gfx950) C ABI for the T1 humanoid LeggedRobot.step() hot path, plus the small kernels
-// around the step (creation-time DR, reset_all, the split post-physics kernels, the stand-alone history shift).
+// around the step (creation-time DR, reset_all, the split post-physics kernels, the history-shift launches).
 //
-// Per env step (t1env_step), normally ONE launch on the caller's stream and no host sync: k_dyn4 in
-// t1env_dynamics.hip runs the 10 substeps, the post-physics epilogue and, in extra workgroups on the CUs the
-// dynamics leave idle, the 65/2-frame history shift.  Split sequence (command-curriculum steps, golden parity):
-//   k_dyn4<FUSED=false> (+ shift workgroups) -> k_post_a -> k_post_b
+// Per env step (t1env_step), normally ONE launch on the caller's stream and no host sync: the step kernel (k_dyn6,
+// t1env_dyn6.hip; k_dyn5 or k_dyn4 where selected) runs the substeps, the 65/2-frame history shift and the
+// post-physics epilogue.  k_dyn4 (and k_dyn5 with DynLaunch::d5_shift) leaves the shift to a second launch on the
+// env's side stream, forked before the step kernel and joined after it (k_shift4c / k_shift5 below).  Split sequence
+// (command-curriculum steps, golden parity):
+//   step kernel<FUSED=false> (|| side shift) -> k_post_a -> k_post_b
 //   k_post_a   : base kinematics, command/ext-force callback, termination, 28 rewards (alphabetical),
 //                episode sums, per-step extras reduction (legged_robot.py:458-489, 509-517, 654-680)
 //   k_post_b   : masked reset_idx, compute_observations -> newest obs/priv frame, last_* bookkeeping, reset-row
 //                zeroing, extras finalisation (legged_robot.py:490-502, t1_dh_stand_env.py:368-559)
-// At large N (no idle CUs) the shift runs as its own launch (k_shift) ahead of the dynamics.
+// Without a step kernel (injected physics, phase B alone) the same shift kernel runs in order on the caller's stream.
 // See include/t1env.h for the ABI and DESIGN.md for layouts and rooflines.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -46,8 +48,7 @@ constexpr int BLOCK = 64;  // one wave per workgroup: 8192 envs -> 128 workgroup
 
 }  // namespace
 
-constexpr int NKERN = 6;  // 0 physics (+ shift), 1 post_a, 2 post_b, 3 shift alone, 4 unused, 5 whole step
-constexpr int SHIFT_BLOCKS = 1024;       // grid of the stand-alone k_shift (256 threads)
+constexpr int NKERN = 6;  // 0 physics (+ in-kernel shift), 1 post_a, 2 post_b, 3 shift launch, 4 unused, 5 whole step
 constexpr int MAX_TIMED = 1 << 14;
 
 struct t1env {
@@ -61,19 +62,19 @@ struct t1env {
   DynModel* d_model;
   t1env_config* d_cfg;
   Terrain terrain;
-  DynLaunch dyn;          // step kernel and shift shape (T1ENV_DYN_KERNEL / T1ENV_SHIFT_BLOCKS override; tuning)
+  DynLaunch dyn;          // step kernel and where its shift runs (T1ENV_DYN_KERNEL / T1ENV_D5_SHIFT override)
   int shift_pending;      // phase A enqueued this step's history shift (phase B alone must run it)
   int fused;              // t1env_step runs the single fused launch (t1env_set_fused; default on)
   uint32_t epoch;         // fused launches so far (tags the shift-unit handoff words)
   uint32_t* d_unit_state; // per shift unit handoff word (fused step)
   int step_timer;         // timing slot of the current step span (phase A start .. phase B end)
   unsigned* d_done;       // k_post_b block-completion counter (its last block finalises the extras)
-  float* d_ep_part;       // k_dyn4's per-workgroup partial extras sums (FusedArgs::ep_part)
+  float* d_ep_part;       // the step kernel's per-workgroup partial extras sums (FusedArgs::ep_part)
   int16_t* d_hmax;        // coarse terrain height bound (Terrain::hmax), built by t1env_set_terrain
   float max_contact_radius;
   SubLog log;             // t1env_set_substep_log (tests): fused steps write it
   int log_on;
-  hipStream_t side;       // k_dyn5's concurrent history shift (k_shift5), forked from / joined to the step's stream
+  hipStream_t side;       // the side-launch history shift (k_shift4c / k_shift5), forked from / joined to the step's stream
   hipEvent_t ev_fork, ev_join;
 };
 
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(BLOCK) void k_post_b(const DynModel* __restrict__ M
   if (live) post_b_env(*Mp, C, B, A, n, do_reset, any_reset);
   // extras["episode"]["terrain_level"] = mean level over all envs after this step's resets (legged_robot.py:1158)
   if (C.custom_origins && any_reset) wave_atomic_add(B.ep_accum + T1_ACC_LEVEL, live ? (float)B.terrain_levels[n] : 0.0f);
-  // reset_idx zeroes the obs / critic history of the reset envs (t1:548-558): k_shift wrote the 65 (2) older
+  // reset_idx zeroes the obs / critic history of the reset envs (t1:548-558): the shift wrote the 65 (2) older
   // frames of every row, so the wave zeroes those of its reset envs here, one row at a time, coalesced
   uint64_t m = __ballot(do_reset);
   while (m) {
@@ -177,27 +178,16 @@ __global__ __launch_bounds__(BLOCK) void k_post_b(const DynModel* __restrict__ M
   }
 }
 
-// history shift for the paths that do not run k_dynamics (injected physics, phase B alone): the same
-// shift_history as k_dynamics' tail workgroups, as its own launch on the caller's stream
-__global__ __launch_bounds__(256) void k_shift(ShiftArgs S) {
-  shift_history(S, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
-}
-
-// chunks per lane in flight in the concurrent shift launch (k_shift5): 93 VGPRs at 4 (8 spills), so one of its waves fits beside
-// a k_dyn5 wave on every SIMD
-constexpr int T1_D5_SHIFT_UNROLL = 4;
 // ---------------------------------------------------------------------------------------------------
-// k_shift5 (compiled here at -O3; the dynamics unit's -O1 spilled its 64-bit addresses): the history shift as a launch of its own, on a second stream beside k_dyn5 (DynLaunch::d5_shift = 1).
-// One 256-thread workgroup per CU with no LDS but its handoff words and <= 96 VGPRs per wave, so it fits next to
-// the k_dyn5 workgroup on every CU (k_dyn5 holds ~405 of a SIMD's 512 registers and 98 KB of LDS without the
-// in-workgroup shift's staging ring) whichever launch the dispatcher places first: the shift's loads and stores
-// issue in the dynamics waves' latency gaps instead of on their instruction stream and their vmcnt.  Each
-// workgroup shifts a contiguous run of SHIFT_UNIT-row units; FUSED: then hands each unit off (unit_handoff, the
-// k_dyn4 protocol, t1env_fused.h) -- whichever of the shift and k_dyn5's epilogue finishes a unit last zeroes its
-// reset rows.  Not FUSED (the split step): k_post_b zeroes them after the caller's join.
+// The history shift as a launch of its own (compiled here at -O3; the dynamics unit's -O1 spilled its 64-bit
+// addresses): on the env's side stream beside k_dyn4 or k_dyn5 (DynLaunch::d5_shift = 1), or alone in stream order
+// where no step kernel runs.  256-thread workgroups with no LDS but their handoff words.  Each workgroup shifts a
+// contiguous run of SHIFT_UNIT-row units, U chunks per lane in flight; FUSED: then hands each unit off (unit_handoff,
+// t1env_fused.h) -- whichever of the shift and the step kernel's epilogue finishes a unit last zeroes its reset rows.
+// Not FUSED: k_post_b zeroes them, after the caller's join or in stream order.
 // ---------------------------------------------------------------------------------------------------
 template <bool FUSED, int U>
-__device__ __forceinline__ void shift_conc_body(ShiftArgs S, FusedArgs FA, int N) {
+__device__ __forceinline__ void shift_launch_body(ShiftArgs S, FusedArgs FA, int N) {
   __shared__ uint32_t words[256];
   const int units = (N + SHIFT_UNIT - 1) / SHIFT_UNIT;
   const int nsw = gridDim.x, j = blockIdx.x;
@@ -224,32 +214,39 @@ __device__ __forceinline__ void shift_conc_body(ShiftArgs S, FusedArgs FA, int N
   }
 }
 
+// k_shift5: beside k_dyn5, one workgroup per CU.  <= 96 VGPRs per wave (93 at 4 chunks per lane in flight), so it fits
+// next to the k_dyn5 workgroup on every CU (k_dyn5 holds ~405 of a SIMD's 512 registers and 98 KB of LDS without the
+// in-workgroup shift's staging ring) whichever launch the dispatcher places first: the shift's loads and stores issue
+// in the dynamics waves' latency gaps instead of on their instruction stream and their vmcnt.
+constexpr int T1_D5_SHIFT_UNROLL = 4;
 template <bool FUSED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5, 8)))
 void k_shift5(ShiftArgs S, FusedArgs FA, int N) {
-  shift_conc_body<FUSED, T1_D5_SHIFT_UNROLL>(S, FA, N);
+  shift_launch_body<FUSED, T1_D5_SHIFT_UNROLL>(S, FA, N);
 }
 
-// k_shift4c: the same concurrent shift beside k_dyn4 (config 5: 32768 envs, fp16 histories).  A k_dyn4
+// k_shift4c: beside k_dyn4, one workgroup per CU (config 5: 32768 envs, fp16 histories).  A k_dyn4
 // wave holds 433 of a SIMD's 512 registers per lane, so a shift wave must stay within 72 (amdgpu_waves_per_eu(7, 8)) to
 // share the SIMD; its 150 KB of LDS (153,608 B with the 28 episode-sum rows staged) leaves room for the shift's 1 KB of
-// handoff words in a CU's 160 KB.
+// handoff words in a CU's 160 KB.  k_shift4c<false> is also the shift of the paths without a step kernel: nothing
+// shares the CUs there, so it runs four workgroups per CU (seven of its waves fit a SIMD).
 constexpr int T1_D4_SHIFT_UNROLL = 3;
 template <bool FUSED>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 8)))
 void k_shift4c(ShiftArgs S, FusedArgs FA, int N) {
-  shift_conc_body<FUSED, T1_D4_SHIFT_UNROLL>(S, FA, N);
+  shift_launch_body<FUSED, T1_D4_SHIFT_UNROLL>(S, FA, N);
 }
 
-int t1_launch_shift5(const ShiftArgs& S, const FusedArgs* fused, int num_envs, int cus, hipStream_t s, bool beside4) {
+int t1_launch_shift(const ShiftArgs& S, const FusedArgs* fused, int num_envs, int cus, hipStream_t s, int beside) {
   const int units = (num_envs + SHIFT_UNIT - 1) / SHIFT_UNIT;
-  const int grid = units < cus ? units : cus;
-  if (beside4) {
-    if (fused) hipLaunchKernelGGL(k_shift4c<true>, dim3(grid), dim3(256), 0, s, S, *fused, num_envs);
-    else hipLaunchKernelGGL(k_shift4c<false>, dim3(grid), dim3(256), 0, s, S, FusedArgs{}, num_envs);
-  } else {
+  const int wgs = beside ? cus : 4 * cus;
+  const int grid = units < wgs ? units : wgs;
+  if (beside == 5) {
     if (fused) hipLaunchKernelGGL(k_shift5<true>, dim3(grid), dim3(256), 0, s, S, *fused, num_envs);
     else hipLaunchKernelGGL(k_shift5<false>, dim3(grid), dim3(256), 0, s, S, FusedArgs{}, num_envs);
+  } else {
+    if (fused) hipLaunchKernelGGL(k_shift4c<true>, dim3(grid), dim3(256), 0, s, S, *fused, num_envs);
+    else hipLaunchKernelGGL(k_shift4c<false>, dim3(grid), dim3(256), 0, s, S, FusedArgs{}, num_envs);
   }
   return (int)hipGetLastError();
 }
@@ -509,21 +506,12 @@ int t1env_create(const t1env_model* model, const t1env_config* cfg, const t1env_
     e->dyn.kernel = t1_dyn_kernel_default(cfg->num_envs, cus, cfg->obs_half != 0);
     if (const char* dk = getenv("T1ENV_DYN_KERNEL"))  // A/B: 4 = k_dyn4, 5 = k_dyn5, 6 = k_dyn6
       if (atoi(dk) >= 4 && atoi(dk) <= 6) e->dyn.kernel = atoi(dk);
-    e->dyn.shift_blocks = 0;
-    if (const char* sb = getenv("T1ENV_SHIFT_BLOCKS"))  // > 0: shift workgroups in the launch; -1: stand-alone shift
-      if (atoi(sb) > 0 || atoi(sb) == -1) e->dyn.shift_blocks = atoi(sb);
-    e->dyn.shift_delay = T1_SHIFT_DELAY_DEFAULT;
     e->dyn.d5_shift = 0;
-    if (const char* ds = getenv("T1ENV_D5_SHIFT"))  // A/B: 1 = the shift as a concurrent launch (k_shift5)
+    if (const char* ds = getenv("T1ENV_D5_SHIFT"))  // A/B: 1 = the shift as a side launch (k_shift5)
       if (atoi(ds) == 0 || atoi(ds) == 1) e->dyn.d5_shift = atoi(ds);
     // k_dyn5's in-workgroup shift moves 1 / decimation of the histories per substep through an LDS ring sized for ten
     // slices (t1env_dyn5.hip SH_ROUNDS); with fewer substeps a slice overruns the ring, so the shift runs as k_shift5
     if (cfg->decimation < 10) e->dyn.d5_shift = 1;
-    e->dyn.d4_shift = 1;
-    if (const char* ds = getenv("T1ENV_D4_SHIFT"))  // A/B: 0 = k_dyn4's stand-alone shift ahead of it, in stream order
-      if (atoi(ds) == 0 || atoi(ds) == 1) e->dyn.d4_shift = atoi(ds);
-    if (const char* sd = getenv("T1ENV_SHIFT_DELAY"))  // tuning: delayed start of the in-launch shift (100 MHz ticks)
-      if (atoi(sd) >= 0) e->dyn.shift_delay = atoi(sd);
   }
   for (int b = 0; b < NB; ++b) e->max_contact_radius = fmaxf(e->max_contact_radius, dm.contact_radius[b]);
   HIP_TRY(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
@@ -592,47 +580,35 @@ static ShiftArgs shift_args(const t1env* e, const t1env_step_args* a) {
                    N * T1_NOBS * T1_HIST, N * T1_NPRIV * T1_CHIST, e->cfg.obs_half ? 1 : 0};
 }
 
-// the history shift as its own launch, in stream order (paths without k_dynamics)
-static int launch_shift(t1env* e, const t1env_step_args* a, hipStream_t s) {
+// The history shift as its own launch on stream s, timed as slot 3 (bench.py: k_shift).  beside: the step kernel it
+// runs next to (t1_launch_shift), 0 = none.
+static int launch_shift(t1env* e, const t1env_step_args* a, const FusedArgs* fa, hipStream_t s, int beside) {
   const int t = t_begin(e, 3, s);
-  hipLaunchKernelGGL(k_shift, dim3(SHIFT_BLOCKS), dim3(256), 0, s, shift_args(e, a));
+  HIP_TRY((hipError_t)t1_launch_shift(shift_args(e, a), fa, e->cfg.num_envs, e->dyn.cus, s, beside));
   t_end(e, t, s);
-  HIP_TRY(hipGetLastError());
   return 0;
 }
 
-// The concurrent shift: k_dyn5 with DynLaunch::d5_shift, or k_dyn4 where its shift would otherwise run as its own
-// launch ahead of it (t1_shift_prelaunch: config 5) with DynLaunch::d4_shift.  The side stream starts after everything
-// enqueued on s so far (fork), runs the shift beside the dynamics launch, and s waits for it before anything after the
-// step (join).  The fused epilogue and the shift hand each 8-row unit off (the k_dyn4 protocol, t1env_fused.h).
-static bool concurrent_shift4(const t1env* e) {
-  return e->dyn.kernel == 4 && e->dyn.d4_shift == 1 && t1_shift_prelaunch(e->cfg.num_envs, e->dyn);
-}
-static bool concurrent_shift(const t1env* e) {
-  return (e->dyn.kernel == 5 && e->dyn.d5_shift == 1) || concurrent_shift4(e);
-}
-static int shift_fork(t1env* e, hipStream_t s) {
-  HIP_TRY(hipEventRecord(e->ev_fork, s));
-  HIP_TRY(hipStreamWaitEvent(e->side, e->ev_fork, 0));
-  return 0;
-}
-static int shift_join(t1env* e, const t1env_step_args* a, const FusedArgs* fa, hipStream_t s) {
-  const int t = t_begin(e, 3, e->side);  // the shift's own span, on its stream (bench.py: k_shift)
-  HIP_TRY((hipError_t)t1_launch_shift5(shift_args(e, a), fa, e->cfg.num_envs, e->dyn.cus, e->side,
-                                       e->dyn.kernel == 4));
-  t_end(e, t, e->side);
-  HIP_TRY(hipEventRecord(e->ev_join, e->side));
-  HIP_TRY(hipStreamWaitEvent(s, e->ev_join, 0));
-  return 0;
-}
-
-// Where the history shift does not run inside the dynamics launch (large N): its own launch ahead of the dynamics in
-// stream order (pre), or the fork of the side stream that runs it beside them (conc; shift_join after the dynamics)
-static int shift_before_dynamics(t1env* e, const t1env_step_args* a, bool pre, bool conc, hipStream_t s) {
-  if (pre && !conc)
-    if (int rc = launch_shift(e, a, s)) return rc;
-  if (conc)
-    if (int rc = shift_fork(e, s)) return rc;
+// The step kernel's launch (timer slot 0) and, for k_dyn4 and for k_dyn5 with DynLaunch::d5_shift, its history shift
+// as a side launch.  The side stream starts after everything enqueued on s so far (fork), runs the shift beside the
+// step kernel, and s waits for it before anything after this (join).  fa (the fused step): the epilogue and the shift
+// hand each 8-row unit off (t1env_fused.h); else the caller's k_post_b zeroes the reset rows after the join.
+static int launch_dynamics(t1env* e, const float* actions, const t1env_step_args* a, const FusedArgs* fa,
+                           hipStream_t s) {
+  const bool side_shift = e->dyn.kernel == 4 || (e->dyn.kernel == 5 && e->dyn.d5_shift == 1);
+  if (side_shift) {
+    HIP_TRY(hipEventRecord(e->ev_fork, s));
+    HIP_TRY(hipStreamWaitEvent(e->side, e->ev_fork, 0));
+  }
+  const int t = t_begin(e, 0, s);
+  HIP_TRY((hipError_t)t1_launch_dynamics(e->d_model, e->d_cfg, e->buf, e->terrain, actions, *a, e->cfg.num_envs,
+                                         shift_args(e, a), e->dyn, fa, s, e->log_on ? &e->log : nullptr));
+  t_end(e, t, s);
+  if (side_shift) {
+    if (int rc = launch_shift(e, a, fa, e->side, e->dyn.kernel)) return rc;
+    HIP_TRY(hipEventRecord(e->ev_join, e->side));
+    HIP_TRY(hipStreamWaitEvent(s, e->ev_join, 0));
+  }
   return 0;
 }
 
@@ -642,27 +618,18 @@ static int launch_physics(t1env* e, const float* actions, const t1env_step_args*
   if (e->log_on && !inj) return fail(T1ENV_E_STATE, "substep log set: only the fused step logs (t1env_set_substep_log)");
   const int N = e->cfg.num_envs;
   e->step_timer = t_begin(e, 5, s);
-  // large N: the shift as its own launch, ahead of the dynamics or beside them (k_post_b zeroes the reset rows after
-  // the join)
-  const bool conc = !inj && concurrent_shift(e);
-  const bool pre = !inj && t1_shift_prelaunch(N, e->dyn);
-  if (int rc = shift_before_dynamics(e, a, pre, conc, s)) return rc;
-  int t = t_begin(e, 0, s);
-  if (inj)
+  if (inj) {  // no step kernel: the injected states, then the shift in stream order
+    const int t = t_begin(e, 0, s);
     hipLaunchKernelGGL(k_physics_injected, dim3(grid(N, BLOCK)), dim3(BLOCK), 0, s, e->d_model, e->d_cfg, e->buf,
                        actions, *a, *inj);
-  else
-    HIP_TRY((hipError_t)t1_launch_dynamics(e->d_model, e->d_cfg, e->buf, e->terrain, actions, *a, N,
-                                           shift_args(e, a), e->dyn, nullptr, s, pre));
-  t_end(e, t, s);
-  HIP_TRY(hipGetLastError());
-  if (conc)
-    if (int rc = shift_join(e, a, nullptr, s)) return rc;
-  if (inj) {
-    if (int rc = launch_shift(e, a, s)) return rc;
+    t_end(e, t, s);
+    HIP_TRY(hipGetLastError());
+    if (int rc = launch_shift(e, a, nullptr, s, 0)) return rc;
+  } else {
+    if (int rc = launch_dynamics(e, actions, a, nullptr, s)) return rc;
   }
   e->shift_pending = 1;
-  t = t_begin(e, 1, s);
+  const int t = t_begin(e, 1, s);
   hipLaunchKernelGGL(k_post_a, dim3(grid(N, BLOCK)), dim3(BLOCK), 0, s, e->d_model, e->d_cfg, e->buf, *a);
   t_end(e, t, s);
   HIP_TRY(hipGetLastError());
@@ -688,7 +655,7 @@ int t1env_step_reset_and_observe(t1env* e, const t1env_step_args* a, void* strea
   const int N = e->cfg.num_envs;
   if (!e->shift_pending) {  // phase B without phase A on this env: shift now, in order
     e->step_timer = -1;
-    if (int rc = launch_shift(e, a, s)) return rc;
+    if (int rc = launch_shift(e, a, nullptr, s, 0)) return rc;
   }
   e->shift_pending = 0;
   int t = t_begin(e, 2, s);
@@ -701,22 +668,12 @@ int t1env_step_reset_and_observe(t1env* e, const t1env_step_args* a, void* strea
   return 0;
 }
 
-// the whole step as one launch (t1env_dynamics.hip, FUSED)
+// the whole step as the step kernel's FUSED launch (beside its side shift, where it has one)
 static int launch_fused(t1env* e, const float* actions, const t1env_step_args* a, hipStream_t s) {
   if (a->obs_slot != 0 && a->obs_slot != 1) return fail(T1ENV_E_ARG, "obs_slot must be 0 or 1");
   e->step_timer = t_begin(e, 5, s);
-  // large N: no idle CUs for shift workgroups -- the shift runs as its own launch, beside the dynamics (concurrent:
-  // the epilogue hands its reset rows off) or first (the epilogue then zeroes them without the handoff)
-  const bool conc = concurrent_shift(e);
-  const bool pre = t1_shift_prelaunch(e->cfg.num_envs, e->dyn);
-  if (int rc = shift_before_dynamics(e, a, pre, conc, s)) return rc;
-  const int t = t_begin(e, 0, s);
-  const FusedArgs FA{e->d_done, e->d_unit_state, ++e->epoch, (pre && !conc) ? 1 : 0, e->d_ep_part};
-  HIP_TRY((hipError_t)t1_launch_dynamics(e->d_model, e->d_cfg, e->buf, e->terrain, actions, *a, e->cfg.num_envs,
-                                         shift_args(e, a), e->dyn, &FA, s, pre, e->log_on ? &e->log : nullptr));
-  t_end(e, t, s);
-  if (conc)
-    if (int rc = shift_join(e, a, &FA, s)) return rc;
+  const FusedArgs FA{e->d_done, e->d_unit_state, ++e->epoch, e->d_ep_part};
+  if (int rc = launch_dynamics(e, actions, a, &FA, s)) return rc;
   t_end(e, e->step_timer, s);
   e->step_timer = -1;
   e->shift_pending = 0;

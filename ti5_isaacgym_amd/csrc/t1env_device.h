@@ -161,13 +161,13 @@ __device__ __forceinline__ void imu_sample(const float raw[8], float out[6]) {
 
 
 // =====================================================================================================
-// history shift: out[n, :F*(H-1)] = in[n, F:] -- a flat shift by F floats of every row of the 66-frame obs
-// and 3-frame critic history; the newest frame (columns >= F*(H-1)) is left to k_post_b, which also zeroes
-// the older frames of reset envs.  One lane per 4 output floats, the shifted source assembled from two
-// aligned 16-B loads.  SHIFT_UNROLL chunks per lane are loaded before any is stored (all loads are
-// unconditional, clamped in bounds), so a lane keeps 8 x 16 B in flight: the shift reaches HBM rate with a
-// few hundred workgroups, which is what k_dynamics' tail workgroups can field (each of its waves holds 240
-// VGPRs).  It reads only the previous step's buffer, so it overlaps the dynamics inside one launch.
+// history shift: out[n, :F*(H-1)] = in[n, F:] -- a flat shift by F elements of every row of the 66-frame obs
+// and 3-frame critic history; the newest frame (columns >= F*(H-1)) is left to post-physics, which also zeroes
+// the older frames of reset envs.  One lane per 16-B output chunk (4 floats or 8 halves), the shifted source
+// assembled from two aligned 16-B loads.  U chunks per lane are loaded before any is stored (all loads are
+// unconditional, clamped in bounds), so a lane keeps 2 U x 16 B in flight.  The shift reads only the previous
+// step's buffer, so it overlaps the dynamics.  This is the shift of the launches outside a step kernel
+// (t1env.hip k_shift5 / k_shift4c); k_dyn5 and k_dyn6 carry their own.
 // =====================================================================================================
 struct ShiftArgs {
   const float* obs_in;
@@ -177,82 +177,24 @@ struct ShiftArgs {
   int64_t total_obs, total_priv;  // elements
   int32_t half;                   // 1: the histories hold fp16 (t1env_config.obs_half; the pointers are fp16 data)
 };
-constexpr int SHIFT_UNROLL = 4;
 
-// Stores of the shift.  SC1 = the agent-coherent flavour (global_store ... sc1): the line leaves the XCD's L2
-// and the store is visible to every XCD once it completes, so a later handoff needs only s_waitcnt, not an L2
-// write-back (MI355X_MICROARCH.md, inter-workgroup visibility).  The fused step uses it for the rows whose
-// reset zeroing may run on another XCD.
+// Stores of the shift, agent-coherent (global_store ... sc1): the line leaves the XCD's L2 and the store is visible
+// to every XCD once it completes, so a later handoff needs only s_waitcnt, not an L2 write-back
+// (MI355X_MICROARCH.md, inter-workgroup visibility).  The fused step needs it for the rows whose reset zeroing may
+// run on another XCD.
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-template <bool SC1> __device__ __forceinline__ void store4(float* p, float4 v) {
-  if constexpr (SC1) {
-    const f32x4 x = {v.x, v.y, v.z, v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(x) : "memory");
-  } else {
-    *reinterpret_cast<float4*>(p) = v;
-  }
+__device__ __forceinline__ void store4(float* p, float4 v) {
+  const f32x4 x = {v.x, v.y, v.z, v.w};
+  asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(x) : "memory");
 }
-template <bool SC1> __device__ __forceinline__ void store1(float* p, float v) {
-  if constexpr (SC1) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  else *p = v;
+__device__ __forceinline__ void store1(float* p, float v) {
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <int F, int H, bool SC1>
-__device__ __forceinline__ void shift_store(float* __restrict__ out, int64_t total, int64_t i, const float4 a,
-                                            const float4 b, int rem) {
-  constexpr int ROW = F * H;
-  const float src[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-  const int64_t row0 = i / ROW;
-  const int col0 = (int)(i - row0 * ROW);
-  // the 4 outputs are all older-frame columns of one row unless the chunk touches a row's newest frame
-  if (col0 + 3 < ROW - F && i + 3 < total) {
-    store4<SC1>(out + i, make_float4(src[rem], src[rem + 1], src[rem + 2], src[rem + 3]));
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int64_t e = i + k;
-    if (e >= total) break;
-    const int64_t row = e / ROW;
-    if ((int)(e - row * ROW) < ROW - F) store1<SC1>(out + e, src[rem + k]);
-  }
-}
-
-// chunks [lo4, hi4) of one history buffer, lane t0 of `stride` lanes
-template <int F, int H, bool SC1 = false, int U = SHIFT_UNROLL>
-__device__ __forceinline__ void shift_range(const float* __restrict__ in, float* __restrict__ out, int64_t total,
-                                            int64_t lo4, int64_t hi4, int64_t t0, int64_t stride) {
-  for (int64_t base = lo4 + t0; base < hi4; base += U * stride) {
-    float4 a[U], b[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t sa = ((base + u * stride) * 4 + F) & ~(int64_t)3;
-      const int64_t sc = sa + 8 <= total ? sa : (total - 8) & ~(int64_t)3;  // tail: aligned in-bounds dummy
-      a[u] = *reinterpret_cast<const float4*>(in + sc);
-      b[u] = *reinterpret_cast<const float4*>(in + sc + 4);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t i4 = base + u * stride;
-      if (i4 >= hi4) break;
-      const int64_t i = i4 * 4, s = i + F, sa = s & ~(int64_t)3;
-      float4 x = a[u], y = b[u];
-      if (sa + 8 > total) {  // the last chunks of the buffer: element loads, zero past the end
-        float t[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t[k] = sa + k < total ? in[sa + k] : 0.0f;
-        x = make_float4(t[0], t[1], t[2], t[3]);
-        y = make_float4(t[4], t[5], t[6], t[7]);
-      }
-      shift_store<F, H, SC1>(out, total, i, x, y, (int)(s - sa));
-    }
-  }
-}
-
-// The in-launch shift's form of shift_range over whole rows [r0, r1): indices relative to the first row fit 32 bits,
-// so the per-chunk row / column split is a 32-bit division by the constant row width instead of a 64-bit one (the
-// fused step's shift workgroups run one wave per SIMD, where that integer work, not HBM, set their rate).
-template <int F, int H, bool SC1, int U>
+// Whole rows [r0, r1) of one fp32 history buffer, lane t0 of `stride` lanes: indices relative to the first row fit 32
+// bits, so the per-chunk row / column split is a 32-bit division by the constant row width (that integer work, not
+// HBM, sets the rate of a shift that runs one wave per SIMD).
+template <int F, int H, int U>
 __device__ __forceinline__ void shift_rows_f32(const float* __restrict__ in, float* __restrict__ out, int64_t total,
                                                int64_t r0, int64_t r1, int t0, int stride) {
   constexpr uint32_t ROW = F * H;
@@ -289,14 +231,14 @@ __device__ __forceinline__ void shift_rows_f32(const float* __restrict__ in, flo
       constexpr int rem = (int)(F & 3u);
       const uint32_t col0 = i - (i / ROW) * ROW;
       if (col0 + 3 < ROW - F && i + 3 < lim) {  // 4 older-frame columns of one row
-        store4<SC1>(out0 + i, make_float4(src[rem], src[rem + 1], src[rem + 2], src[rem + 3]));
+        store4(out0 + i, make_float4(src[rem], src[rem + 1], src[rem + 2], src[rem + 3]));
         continue;
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const uint32_t e = i + k;
         if (e >= lim) break;
-        if (e - (e / ROW) * ROW < ROW - F) store1<SC1>(out0 + e, src[rem + k]);
+        if (e - (e / ROW) * ROW < ROW - F) store1(out0 + e, src[rem + k]);
       }
     }
   }
@@ -307,72 +249,14 @@ __device__ __forceinline__ void shift_rows_f32(const float* __restrict__ in, flo
 // constant (every chunk starts on a multiple of 8), so the output chunk is four funnel shifts of 32-bit words
 // (v_alignbyte) for odd F, or plain word moves for even F.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-template <bool SC1> __device__ __forceinline__ void store16B(uint16_t* p, u32x4 v) {
-  if constexpr (SC1) asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
-  else *reinterpret_cast<u32x4*>(p) = v;
+__device__ __forceinline__ void store16B(uint16_t* p, u32x4 v) {
+  asm volatile("global_store_dwordx4 %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
 }
-template <bool SC1> __device__ __forceinline__ void store2B(uint16_t* p, uint16_t v) {
-  if constexpr (SC1) {
-    const uint32_t w = v;
-    asm volatile("global_store_short %0, %1, off sc1" : : "v"(p), "v"(w) : "memory");
-  } else {
-    *p = v;
-  }
+__device__ __forceinline__ void store2B(uint16_t* p, uint16_t v) {
+  const uint32_t w = v;
+  asm volatile("global_store_short %0, %1, off sc1" : : "v"(p), "v"(w) : "memory");
 }
-template <int F, int H, bool SC1 = false, int U = SHIFT_UNROLL>
-__device__ __forceinline__ void shift_range_h(const uint16_t* __restrict__ in, uint16_t* __restrict__ out,
-                                              int64_t total, int64_t lo8, int64_t hi8, int64_t t0, int64_t stride) {
-  constexpr int ROW = F * H, REM = F % 8, M = REM / 2;
-  for (int64_t base = lo8 + t0; base < hi8; base += U * stride) {
-    u32x4 a[U], b[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t sa = ((base + u * stride) * 8 + F) & ~(int64_t)7;
-      const int64_t sc = sa + 16 <= total ? sa : (total - 16) & ~(int64_t)7;  // tail: aligned in-bounds dummy
-      a[u] = *reinterpret_cast<const u32x4*>(in + sc);
-      b[u] = *reinterpret_cast<const u32x4*>(in + sc + 8);
-    }
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t c8 = base + u * stride;
-      if (c8 >= hi8) break;
-      const int64_t i = c8 * 8, sa = (i + F) & ~(int64_t)7;
-      uint32_t w[8] = {a[u].x, a[u].y, a[u].z, a[u].w, b[u].x, b[u].y, b[u].z, b[u].w};
-      if (sa + 16 > total) {  // the last chunks of the buffer: element loads, zero past the end
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const uint32_t lo = sa + 2 * k < total ? in[sa + 2 * k] : 0u;
-          const uint32_t hi = sa + 2 * k + 1 < total ? in[sa + 2 * k + 1] : 0u;
-          w[k] = lo | (hi << 16);
-        }
-      }
-      u32x4 o;
-      if constexpr (REM % 2 == 0) {
-        o = u32x4{w[M], w[M + 1], w[M + 2], w[M + 3]};
-      } else {  // halves REM .. REM + 7 = the upper half of word M, ..., the lower half of word M + 4
-        o = u32x4{__builtin_amdgcn_alignbyte(w[M + 1], w[M], 2), __builtin_amdgcn_alignbyte(w[M + 2], w[M + 1], 2),
-                  __builtin_amdgcn_alignbyte(w[M + 3], w[M + 2], 2), __builtin_amdgcn_alignbyte(w[M + 4], w[M + 3], 2)};
-      }
-      const int64_t row0 = i / ROW;
-      const int col0 = (int)(i - row0 * ROW);
-      if (col0 + 7 < ROW - F && i + 7 < total) {
-        store16B<SC1>(out + i, o);
-        continue;
-      }
-      const uint32_t ow[4] = {o.x, o.y, o.z, o.w};
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const int64_t e = i + k;
-        if (e >= total) break;
-        const int64_t row = e / ROW;
-        if ((int)(e - row * ROW) < ROW - F) store2B<SC1>(out + e, (uint16_t)(ow[k / 2] >> (16 * (k & 1))));
-      }
-    }
-  }
-}
-
-// shift_range_h's in-launch form over whole rows [r0, r1) with 32-bit local indices (see shift_rows_f32)
-template <int F, int H, bool SC1, int U>
+template <int F, int H, int U>
 __device__ __forceinline__ void shift_rows_f16(const uint16_t* __restrict__ in, uint16_t* __restrict__ out,
                                                int64_t total, int64_t r0, int64_t r1, int t0, int stride) {
   constexpr uint32_t ROW = F * H, REM = F % 8, M = REM / 2;
@@ -414,7 +298,7 @@ __device__ __forceinline__ void shift_rows_f16(const uint16_t* __restrict__ in, 
       }
       const uint32_t col0 = i - (i / ROW) * ROW;
       if (col0 + 7 < ROW - F && i + 7 < lim) {
-        store16B<SC1>(out0 + i, o);
+        store16B(out0 + i, o);
         continue;
       }
       const uint32_t ow[4] = {o.x, o.y, o.z, o.w};
@@ -422,42 +306,28 @@ __device__ __forceinline__ void shift_rows_f16(const uint16_t* __restrict__ in, 
       for (int k = 0; k < 8; ++k) {
         const uint32_t e = i + k;
         if (e >= lim) break;
-        if (e - (e / ROW) * ROW < ROW - F) store2B<SC1>(out0 + e, (uint16_t)(ow[k / 2] >> (16 * (k & 1))));
+        if (e - (e / ROW) * ROW < ROW - F) store2B(out0 + e, (uint16_t)(ow[k / 2] >> (16 * (k & 1))));
       }
     }
   }
 }
 
-// lane `t0` of `stride` lanes: the obs history, then the critic history
-__device__ __forceinline__ void shift_history(const ShiftArgs& S, int64_t t0, int64_t stride) {
-  if (S.half) {
-    shift_range_h<T1_NOBS, T1_HIST>(reinterpret_cast<const uint16_t*>(S.obs_in), reinterpret_cast<uint16_t*>(S.obs_out),
-                                    S.total_obs, 0, (S.total_obs + 7) / 8, t0, stride);
-    shift_range_h<T1_NPRIV, T1_CHIST>(reinterpret_cast<const uint16_t*>(S.priv_in),
-                                      reinterpret_cast<uint16_t*>(S.priv_out), S.total_priv, 0, (S.total_priv + 7) / 8,
-                                      t0, stride);
-    return;
-  }
-  shift_range<T1_NOBS, T1_HIST>(S.obs_in, S.obs_out, S.total_obs, 0, (S.total_obs + 3) / 4, t0, stride);
-  shift_range<T1_NPRIV, T1_CHIST>(S.priv_in, S.priv_out, S.total_priv, 0, (S.total_priv + 3) / 4, t0, stride);
-}
-
 // the rows [r0, r1) of both histories (r0 a multiple of 8, so both row ranges start on a 16-B chunk of either
-// element size), with agent-coherent (sc1) stores
-template <int U = SHIFT_UNROLL>
+// element size)
+template <int U>
 __device__ __forceinline__ void shift_rows_range_sc1(const ShiftArgs& S, int64_t r0, int64_t r1, int64_t t0,
                                                  int64_t stride) {
   if (S.half) {
-    shift_rows_f16<T1_NOBS, T1_HIST, true, U>(reinterpret_cast<const uint16_t*>(S.obs_in),
-                                              reinterpret_cast<uint16_t*>(S.obs_out), S.total_obs, r0, r1, (int)t0,
-                                              (int)stride);
-    shift_rows_f16<T1_NPRIV, T1_CHIST, true, U>(reinterpret_cast<const uint16_t*>(S.priv_in),
-                                                reinterpret_cast<uint16_t*>(S.priv_out), S.total_priv, r0, r1, (int)t0,
-                                                (int)stride);
+    shift_rows_f16<T1_NOBS, T1_HIST, U>(reinterpret_cast<const uint16_t*>(S.obs_in),
+                                        reinterpret_cast<uint16_t*>(S.obs_out), S.total_obs, r0, r1, (int)t0,
+                                        (int)stride);
+    shift_rows_f16<T1_NPRIV, T1_CHIST, U>(reinterpret_cast<const uint16_t*>(S.priv_in),
+                                          reinterpret_cast<uint16_t*>(S.priv_out), S.total_priv, r0, r1, (int)t0,
+                                          (int)stride);
     return;
   }
-  shift_rows_f32<T1_NOBS, T1_HIST, true, U>(S.obs_in, S.obs_out, S.total_obs, r0, r1, (int)t0, (int)stride);
-  shift_rows_f32<T1_NPRIV, T1_CHIST, true, U>(S.priv_in, S.priv_out, S.total_priv, r0, r1, (int)t0, (int)stride);
+  shift_rows_f32<T1_NOBS, T1_HIST, U>(S.obs_in, S.obs_out, S.total_obs, r0, r1, (int)t0, (int)stride);
+  shift_rows_f32<T1_NPRIV, T1_CHIST, U>(S.priv_in, S.priv_out, S.total_priv, r0, r1, (int)t0, (int)stride);
 }
 
 // zero `count` elements of row `row` (row width `width`) of a history buffer, fp32 or fp16

@@ -1,5 +1,5 @@
 // t1env_dynamics.hip -- the env step's main launch: the decimation loop with the articulated-body solver
-// (legged_robot.py:399-434 + Isaac Gym simulate()), the history shift, and in the fused step post-physics.
+// (legged_robot.py:399-434 + Isaac Gym simulate()) and, in the fused step, post-physics.
 // Its own translation unit because it is compiled at -O1 (build.py; -O2/-O3 measure the same since round 2 and are
 // correct too (tests/test_gpu_opt_levels.py runs the -O3 build through the fp64 dynamics check and the product replay).
 #include <hip/hip_runtime.h>
@@ -16,9 +16,9 @@
 using namespace t1;
 
 // ---------------------------------------------------------------------------------------------------
-// The launch: ceil(N/64) dynamics workgroups of 64 envs, then history-shift workgroups (blockIdx >= dyn_blocks,
-// t1env_device.h).  The dynamics fill at most half the CUs at 8192 envs, so the HBM-bound shift streams on the rest
-// of the chip inside the same launch -- no second stream, no cross-stream events on the step path.
+// The launch: ceil(N/64) dynamics workgroups of 64 envs.  The HBM-bound history shift is a launch of its own on the
+// env's side stream (k_shift4c, t1env.hip), forked before this launch and joined after it: its waves fit beside a
+// k_dyn4 wave on every SIMD, or stream on the CUs the dynamics leave idle.
 //
 //   k_dyn4 (4 waves / 64 envs): waves 0/1 are the leg waves -- wave 0 runs every env's left leg, wave 1 the right
 //     leg (the leg index is wave-uniform, so model reads are scalar loads) -- running the articulated-body passes
@@ -37,7 +37,7 @@ using namespace t1;
 //   * reset_idx's "resample commands of every env if any env reset" has no global dependency here: for an env
 //     that did not reset, the second resample repeats post_a's (same episode step, same keyed draws), so each
 //     env needs only its own reset flag;
-//   * zeroing the history rows of reset envs must follow the shift of those rows, which other workgroups do
+//   * zeroing the history rows of reset envs must follow the shift of those rows, which the shift launch does
 //     concurrently.  The shift is cut into units of SHIFT_UNIT rows, and each unit has a handoff word
 //     (epoch-tagged): the shift workgroup sets bit 0 once the unit is shifted, the dynamics workgroup sets
 //     bit 1 together with the unit's 8-bit reset mask.  Whoever sets the second bit zeroes the unit's reset
@@ -54,47 +54,7 @@ using namespace t1;
 
 constexpr int DYN_ENVS = 64;
 constexpr int D4_BLOCK = 4 * DYN_ENVS;
-// chunks per lane in flight in the in-launch shift: the shift workgroups run one wave per SIMD on the CUs the dynamics
-// leave idle, so they need deep per-lane batches (r02u: 8 -> 16 took the shift alone from 114 to 106 us at 8192 envs)
-constexpr int T1_FUSED_SHIFT_UNROLL = 16;
 static_assert(DYN_ENVS % SHIFT_UNIT == 0, "a dynamics workgroup owns whole shift units");
-
-// A history-shift workgroup (j of nsw) of BS threads; `words` is LDS scratch of >= BS uint32.
-template <bool FUSED, int BS>
-__device__ __forceinline__ void shift_workgroup(const ShiftArgs& S, const FusedArgs& FA, int N, int j, int nsw,
-                                                uint32_t* words, int delay) {
-  if (delay > 0) {  // let the dynamics workgroups' prologue loads go first (wave-uniform; the 100 MHz real-time clock)
-    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-    while (__builtin_amdgcn_s_memrealtime() - t0 < (uint64_t)delay) __builtin_amdgcn_s_sleep(32);
-  }
-  if constexpr (!FUSED) {
-    shift_history(S, (int64_t)j * BS + threadIdx.x, (int64_t)nsw * BS);
-  } else {
-    // a contiguous run of units per workgroup, shifted as one flat row range: each lane keeps
-    // T1_FUSED_SHIFT_UNROLL x 32 B of loads in flight, enough for HBM rate from one workgroup per CU on the CUs
-    // the dynamics leave idle (a per-unit loop re-starts its unrolled batches every 8 rows and wastes their tails)
-    const int units = (N + SHIFT_UNIT - 1) / SHIFT_UNIT;
-    const int per = (units + nsw - 1) / nsw;
-    const int u0 = j * per < units ? j * per : units, u1 = u0 + per < units ? u0 + per : units;
-    const int mine = u1 - u0;  // units of this workgroup
-    if (mine > 0) {
-      const int64_t r0 = (int64_t)u0 * SHIFT_UNIT, r1 = (int64_t)u1 * SHIFT_UNIT < N ? (int64_t)u1 * SHIFT_UNIT : N;
-      shift_rows_range_sc1<T1_FUSED_SHIFT_UNROLL>(S, r0, r1, threadIdx.x, BS);
-    }
-    // every lane's sc1 stores complete (visible at agent scope) before any handoff
-    __builtin_amdgcn_s_waitcnt(0);
-    __syncthreads();
-    for (int k0 = 0; k0 < mine; k0 += BS) {
-      const int k = k0 + (int)threadIdx.x;
-      if (k < mine) words[threadIdx.x] = unit_handoff(FA.unit_state + u0 + k, FA.epoch, HANDOFF_SHIFT);
-      __syncthreads();
-      const int cnt = mine - k0 < BS ? mine - k0 : BS;
-      for (int i = 0; i < cnt; ++i)
-        if (handoff_complete(words[i])) zero_unit_resets(S, u0 + k0 + i, words[i], threadIdx.x, BS);
-      __syncthreads();
-    }
-  }
-}
 
 // ---------------------------------------------------------------------------------------------------
 // k_dyn4: 4 waves per 64 envs (see the top of the file).  Per substep, leg wave | contact helper wave:
@@ -251,14 +211,9 @@ __device__ __forceinline__ void exchange_self_bodies(const DynModel& M, Dyn4Lds&
 template <bool HF, bool FUSED>
 __global__ __launch_bounds__(D4_BLOCK) void k_dyn4(const DynModel* __restrict__ Mp, const t1env_config* __restrict__ Cp,
                                                    t1env_buffers B, Terrain Tin, const float* __restrict__ actions,
-                                                   t1env_step_args A, ShiftArgs S, int dyn_blocks, FusedArgs FA,
-                                                   SubLog LG, int shift_delay) {
+                                                   t1env_step_args A, ShiftArgs S, FusedArgs FA, SubLog LG) {
   __shared__ Dyn4Lds lds;
-  if ((int)blockIdx.x >= dyn_blocks) {
-    shift_workgroup<FUSED, D4_BLOCK>(S, FA, Cp->num_envs, blockIdx.x - dyn_blocks, gridDim.x - dyn_blocks,
-                                     reinterpret_cast<uint32_t*>(&lds.xch[0][0][0]), shift_delay);
-    return;
-  }
+  const int dyn_blocks = (int)gridDim.x;
   Terrain T = Tin;
   T.type = HF ? 2 : 0;
   const t1env_config& C = *Cp;
@@ -554,46 +509,28 @@ __global__ __launch_bounds__(D4_BLOCK) void k_dyn4(const DynModel* __restrict__ 
 
 // k_dyn6 at 8192 trimesh envs (one round of 32-env workgroups on 256 CUs): 0.127 ms, k_dyn5 0.141, k_dyn4 0.150.
 // Above one round k_dyn6's rounds still beat k_dyn4's 64-env workgroups with fp32 histories (r05full: 16384 trimesh
-// 0.247 vs 0.268 ms, 32768 hf + push 0.485 vs 0.519), but not with fp16 histories, where k_dyn4's stand-alone shift
+// 0.247 vs 0.268 ms, 32768 hf + push 0.485 vs 0.519), but not with fp16 histories, where k_dyn4's side shift
 // launch halves and k_dyn4's 64 envs per workgroup are the better throughput (r05cfg5: 32768 hf + push 0.437 vs 0.471,
 // 16384 0.216 vs 0.240).  T1ENV_DYN_KERNEL=4|5|6 overrides (A/B).
 int t1_dyn_kernel_default(int num_envs, int cus, bool obs_half) {
   return obs_half && (num_envs + 31) / 32 > cus ? 4 : 6;
 }
 
-constexpr int MIN_SHIFT_BLOCKS = 64;
-bool t1_shift_prelaunch(int num_envs, const DynLaunch& cfg) {
-  if (cfg.kernel >= 5) return false;        // k_dyn5 / k_dyn6: every workgroup shifts its own rows
-  if (cfg.shift_blocks < 0) return true;   // forced stand-alone shift (tuning: T1ENV_SHIFT_BLOCKS=-1)
-  if (cfg.shift_blocks > 0) return false;  // explicit shift-workgroup count (tuning)
-  const int dyn_blocks = (num_envs + DYN_ENVS - 1) / DYN_ENVS;
-  return cfg.cus - dyn_blocks < MIN_SHIFT_BLOCKS;
-}
-
+// The launch of the step kernel DynLaunch::kernel names.  k_dyn4's grid is its dynamics workgroups only: its history
+// shift is the caller's side launch (t1_launch_shift).
 int t1_launch_dynamics(const DynModel* d_model, const t1env_config* d_cfg, const t1env_buffers& B, const Terrain& T,
                        const float* actions, const t1env_step_args& A, int num_envs, const ShiftArgs& S,
-                       const DynLaunch& cfg, const FusedArgs* fused, hipStream_t s, bool shift_prelaunched,
-                       const SubLog* log) {
+                       const DynLaunch& cfg, const FusedArgs* fused, hipStream_t s, const SubLog* log) {
   if (cfg.kernel == 6) return t1_launch_dyn6(d_model, d_cfg, B, T, actions, A, num_envs, S, fused, s, log);
-  if (cfg.kernel == 5)  // the shift in the workgroup (d5_shift 0) or the caller's concurrent k_shift5 launch (1)
+  if (cfg.kernel == 5)  // the shift in the workgroup (d5_shift 0) or the caller's side launch (1)
     return t1_launch_dyn5(d_model, d_cfg, B, T, actions, A, num_envs, S, fused, s, log, cfg.d5_shift == 0);
-  const int dyn_blocks = (num_envs + DYN_ENVS - 1) / DYN_ENVS;
-  // history-shift workgroups: the workgroup slots the dynamics leave free (a k_dyn4 wave holds a whole SIMD's
-  // registers: one workgroup per CU), at least MIN_SHIFT_BLOCKS; none when the caller ran the shift as its own
-  // launch (t1_shift_prelaunch)
-  int shift_blocks = cfg.shift_blocks > 0 ? cfg.shift_blocks : cfg.cus - dyn_blocks;
-  if (shift_blocks < MIN_SHIFT_BLOCKS) shift_blocks = MIN_SHIFT_BLOCKS;
-  if (shift_prelaunched) shift_blocks = 0;
-  // the shift's delayed start only where it has slack: as many shift workgroups as dynamics ones (N <= 8192 on 256 CUs)
-  const int shift_delay = shift_blocks >= dyn_blocks ? cfg.shift_delay : 0;
   const FusedArgs FA = fused ? *fused : FusedArgs{};
   const SubLog LG = log ? *log : SubLog{};
-  const dim3 grid(dyn_blocks + shift_blocks);
+  const dim3 grid((num_envs + DYN_ENVS - 1) / DYN_ENVS);
   const bool hf = T.type != 0;
   if (log && !fused) return (int)hipErrorInvalidValue;  // the substep log: fused steps only (the caller checks)
 #define T1_LAUNCH(HF, FU) \
-  hipLaunchKernelGGL((k_dyn4<HF, FU>), grid, dim3(D4_BLOCK), 0, s, d_model, d_cfg, B, T, actions, A, S, dyn_blocks, FA, LG, \
-                     shift_delay)
+  hipLaunchKernelGGL((k_dyn4<HF, FU>), grid, dim3(D4_BLOCK), 0, s, d_model, d_cfg, B, T, actions, A, S, FA, LG)
   if (fused) { if (hf) T1_LAUNCH(true, true); else T1_LAUNCH(false, true); }
   else { if (hf) T1_LAUNCH(true, false); else T1_LAUNCH(false, false); }
 #undef T1_LAUNCH

@@ -20,8 +20,8 @@ constexpr int K_SHANK = 3, K_FOOT = 5;
 static_assert(T1_LEG_CONTACT_MASK == ((1 << K_SHANK) | (1 << K_FOOT)), "the step kernels assume shank + foot contacts");
 constexpr int XCH = 27;  // Sym6 (21) + rhs (6)
 
-// ---- the in-launch history shift's reset-row handoff (k_dyn4: the shift runs in other workgroups, possibly on
-// another XCD).  Handoff word of a shift unit: [epoch tag : 22][reset mask : 8][dynamics done : 1][shift done : 1].
+// ---- the side-launch history shift's reset-row handoff (k_shift4c / k_shift5: the shift runs in another launch,
+// possibly on another XCD).  Handoff word of a shift unit: [epoch tag : 22][reset mask : 8][dynamics done : 1][shift done : 1].
 // Set `bits` (state bits and, from the dynamics side, the mask) for this epoch; returns the new word.  The word is
 // complete when both state bits are set; the party whose update completes it zeroes the unit's reset rows.
 constexpr uint32_t HANDOFF_SHIFT = 1u, HANDOFF_DYN = 2u;
@@ -47,16 +47,16 @@ __device__ __forceinline__ void zero_unit_resets(const ShiftArgs& S, int u, uint
   }
 }
 
-// After post-physics: the reset rows of the workgroup's NE envs.  INWG (k_dyn5): the workgroup shifted its own rows
-// earlier in the launch, so it zeroes its reset rows itself (the shift's stores completed before the epilogue
-// barrier); likewise when the shift ran as its own launch before this one (FA.shift_done).  Otherwise (k_dyn4) each
-// of the workgroup's shift units is handed off with its 8-bit reset mask.
+// After post-physics: the reset rows of the workgroup's NE envs.  INWG (k_dyn5, k_dyn6): the workgroup shifted its own
+// rows earlier in the launch, so it zeroes its reset rows itself (the shift's stores completed before the epilogue
+// barrier).  Otherwise (the shift is a side launch) each of the workgroup's shift units is handed off with its 8-bit
+// reset mask.
 template <int NE, bool INWG>
 __device__ __forceinline__ void epilogue_handoff(const t1env_config& C, const ShiftArgs& S, const FusedArgs& FA, int lane,
                                                  bool do_reset, bool active) {
   const int N = C.num_envs;
   const unsigned long long m = __ballot(do_reset && active);
-  if (INWG || FA.shift_done) {
+  if (INWG) {
     unsigned long long todo = m;
     while (todo) {
       const int l = __ffsll(todo) - 1;

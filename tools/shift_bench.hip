@@ -1,4 +1,4 @@
-// Microbenchmark of the history shift (t1env_device.h shift_history) at the config-5 size: variants of the
+// Microbenchmark of the history shift (t1env_device.h shift_rows_range_sc1) at the config-5 size: variants of the
 // load shape, grid and cache policy against a plain float4 copy of the same bytes (the achievable HBM rate).
 //   hipcc --offload-arch=gfx950 -O3 -o /tmp/shift_bench tools/shift_bench.hip && /tmp/shift_bench [num_envs]
 // Prints one line per variant: average kernel time (HIP events, 50 launches) and algorithmic GB/s
@@ -22,8 +22,12 @@
 
 using namespace t1;
 
+// the library's shift as its launches run it: each workgroup a contiguous run of 8-row units (t1env.hip)
 __global__ __launch_bounds__(256) void k_cur(ShiftArgs S) {
-  shift_history(S, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, (int64_t)gridDim.x * blockDim.x);
+  const int64_t rows = S.total_obs / (T1_NOBS * T1_HIST);
+  const int64_t units = (rows + 7) / 8, per = (units + gridDim.x - 1) / gridDim.x;
+  const int64_t u0 = blockIdx.x * per < units ? blockIdx.x * per : units, u1 = u0 + per < units ? u0 + per : units;
+  if (u1 > u0) shift_rows_range_sc1<4>(S, u0 * 8, u1 * 8 < rows ? u1 * 8 : rows, threadIdx.x, 256);
 }
 
 // unaligned 16-B source loads (dword-aligned; gfx9 global loads take them), aligned 16-B stores

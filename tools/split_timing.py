@@ -1,6 +1,7 @@
-"""Dev probe: per-launch HIP-event times of the step's parts, with the history shift as its own launch
-(T1ENV_SHIFT_BLOCKS=-1 is set here): fused (dynamics + post-physics epilogue in one launch) and split (dynamics
-launch, then k_post_a / k_post_b).  fused - split dynamics = what the in-launch epilogue adds.
+"""Dev probe: per-launch HIP-event times of the step's parts: fused (dynamics + post-physics epilogue in one launch)
+and split (dynamics launch, then k_post_a / k_post_b).  fused - split dynamics = what the epilogue adds to the step
+kernel.  With T1ENV_DYN_KERNEL=4 (or 5 with T1ENV_D5_SHIFT=1) the history shift is a side launch with a span of its
+own (k_shift); k_dyn6 and k_dyn5 carry it inside the dynamics span.
 
     python tools/split_timing.py [--num-envs 8192] [--mesh trimesh] [--steps 200]
 """
@@ -9,7 +10,6 @@ import json
 import os
 import sys
 
-os.environ.setdefault("T1ENV_SHIFT_BLOCKS", "-1")
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
