@@ -282,9 +282,10 @@ int t1env_step_physics_and_rewards(t1env* env, const float* actions, const t1env
 int t1env_step_reset_and_observe(t1env* env, const t1env_step_args* args, void* stream);
 int t1env_step_injected(t1env* env, const float* actions, const t1env_step_args* args, const t1env_injected* inj,
                         void* stream);
-/* Height scan (terrain.measure_heights = True; inactive in DHT1StandCfg).  With it on, a step
- * runs the split sequence with the scan between the phases, as the reference orders it:
- *   t1env_step_physics_and_rewards -> t1env_measure_heights -> t1env_step_reset_and_observe -> t1env_critic_heights
+/* Height scan (terrain.measure_heights = True; inactive in DHT1StandCfg).
+ * After a real-dynamics step it is ONE launch, t1env_height_scan (below).  The injected-physics hook runs the split
+ * sequence with the scan between the phases, as the reference orders it (fp32 histories only):
+ *   t1env_step_injected -> t1env_measure_heights -> t1env_step_reset_and_observe -> t1env_critic_heights
  * t1env_measure_heights replaces LeggedRobot._get_heights (legged_robot.py:1551-1587, called from the callback,
  *   t1_dh_stand_env.py:190-191): measured (N, npts) from the post-physics, pre-reset base pose in root_states and
  *   points (npts, 2) = the base-frame (x, y) of _init_height_points (legged_robot.py:1535-1549); zeros on a plane.
@@ -295,6 +296,19 @@ int t1env_step_injected(t1env* env, const float* actions, const t1env_step_args*
 int t1env_measure_heights(t1env* env, const float* points, int32_t npts, float* measured, void* stream);
 int t1env_critic_heights(t1env* env, int32_t obs_slot, int32_t npts, float scale, const float* measured,
                          const float* prev, float* out, void* stream);
+/* The scan and the critic-history assembly as one launch, after t1env_step (fused or split) of the same obs_slot, in
+ * stream order: measured (N, npts) fp32 and out (N, 3, 73 + npts) as the pair above defines them, with the same
+ * arithmetic.  prev and out are fp32, or fp16 when cfg.obs_half (copied values pass through unchanged; the newest
+ * heights frame is computed in fp32 and rounded once, to nearest even, so the fp16 out is the fp32 out rounded); they
+ * must be two different buffers.
+ * It reads the pre-reset base pose from body 0 of rigid_state, not from root_states: every step kernel reports the
+ * post-physics root row to both, and post-physics and the reset write root_states only.  It therefore follows a
+ * real-dynamics step only; t1env_step_injected's rigid rows are the caller's synthetic ones, so that hook keeps
+ * t1env_measure_heights / t1env_critic_heights between its phases.  The post-reset root height of the newest frame and
+ * this step's reset flags come from root_states / reset_buf.  Errors: T1ENV_E_ARG for a bad argument, T1ENV_E_STATE
+ * for a height-field terrain that was never set. */
+int t1env_height_scan(t1env* env, int32_t obs_slot, const float* points, int32_t npts, float scale, float* measured,
+                      const void* prev, void* out, void* stream);
 /* t1env_step runs the whole step as ONE launch by default (fused): the history shift and post-physics ride in
  * the step kernel (post-physics in its epilogue; with k_dyn4 the shift is the side launch beside it).  enable = 0 makes t1env_step run the split sequence
  * (physics_and_rewards + reset_and_observe) instead; both give the same buffers.  The split entry points are
@@ -305,7 +319,7 @@ int t1env_set_substep_log(t1env* env, const t1env_substep_log* log);
  * 0 the step kernel incl. an in-kernel history shift (or the injected-physics kernel), 1 k_post_a, 2 k_post_b (its
  * last block also finalises the extras), 3 the history shift as its own launch (beside k_dyn4 / k_dyn5 on the side
  * stream, or in stream order for injected physics and phase B without phase A),
- * 4 unused, 5 the whole step (phase A start .. phase B end).  get_timing synchronises and returns summed milliseconds and launch counts per id since
+ * 4 the height scan (t1env_height_scan), 5 the whole step (phase A start .. phase B end).  get_timing synchronises and returns summed milliseconds and launch counts per id since
  * the last enable. */
 #define T1ENV_NTIMERS 6
 /* enable: bit 0 = record events from now on; bit 1 = keep (do not clear) the events recorded so far */

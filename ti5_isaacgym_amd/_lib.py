@@ -96,7 +96,8 @@ class SubstepLog(C.Structure):
 EXPORTS = ["t1env_create", "t1env_destroy", "t1env_init", "t1env_set_terrain", "t1env_reset_all", "t1env_step",
            "t1env_step_physics_and_rewards", "t1env_step_reset_and_observe", "t1env_step_injected",
            "t1env_set_fused", "t1env_set_timing", "t1env_get_timing", "t1env_last_error", "t1env_version",
-           "t1env_measure_heights", "t1env_critic_heights", "t1env_reset_idx", "t1env_set_substep_log"]
+           "t1env_measure_heights", "t1env_critic_heights", "t1env_reset_idx", "t1env_set_substep_log",
+           "t1env_height_scan"]
 
 # include/t1policy.h: the DH policy's HIP kernels, in the same library
 POLICY_EXPORTS = ["t1policy_conv1d_forward", "t1policy_history_rows", "t1policy_conv1d_frag_bytes",
@@ -144,6 +145,7 @@ def load():
         "t1env_measure_heights": ([vp, vp, i32, vp, vp], C.c_int),
         "t1env_reset_idx": ([vp, vp, P(StepArgs), vp], C.c_int),
         "t1env_critic_heights": ([vp, i32, i32, f32, vp, vp, vp, vp], C.c_int),
+        "t1env_height_scan": ([vp, i32, vp, i32, f32, vp, vp, vp, vp], C.c_int),
         "t1policy_conv1d_forward": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], C.c_int),
         "t1policy_history_rows": ([vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp], C.c_int),
         "t1policy_conv1d_frag_bytes": ([], C.c_int),

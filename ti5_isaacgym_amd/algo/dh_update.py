@@ -310,7 +310,8 @@ class DHPPO:
         self.actor_critic.reset(dones)
 
     def compute_returns(self, last_critic_obs):
-        last_values = self.actor_critic.evaluate(last_critic_obs).detach()
+        # .float(): an env with fp16 histories hands over an fp16 critic observation (a no-op for fp32)
+        last_values = self.actor_critic.evaluate(last_critic_obs.float()).detach()
         self.storage.compute_returns(last_values, self.gamma, self.lam)
 
     def _adapt_lr(self, mu, sigma, old_mu, old_sigma):

@@ -48,7 +48,7 @@ constexpr int BLOCK = 64;  // one wave per workgroup: 8192 envs -> 128 workgroup
 
 }  // namespace
 
-constexpr int NKERN = 6;  // 0 physics (+ in-kernel shift), 1 post_a, 2 post_b, 3 shift launch, 4 unused, 5 whole step
+constexpr int NKERN = 6;  // 0 physics (+ in-kernel shift), 1 post_a, 2 post_b, 3 shift launch, 4 height scan, 5 whole step
 constexpr int MAX_TIMED = 1 << 14;
 
 struct t1env {
@@ -273,25 +273,19 @@ __global__ __launch_bounds__(256) void k_terrain_level_sum(t1env_buffers B, cons
 // roundings (no FMA contraction, true division).  One thread per (env, point); reads root_states, which
 // t1env_step_physics_and_rewards left at the post-physics, pre-reset pose the reference's callback samples.
 // k_critic_heights assembles the critic history with heights (t1_dh_stand_env.py:466-468, 548-558): one
-// thread per (env, column) of (N, 3, 73 + npts).
+// thread per (env, column) of (N, 3, 73 + npts).  This pair serves the injected-physics hook (fp32 only); a
+// real-dynamics step runs k_height_scan below, one launch after the step, fp32 or fp16.
 // -----------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_measure_heights(const float* __restrict__ root, const float* __restrict__ pts,
-                                                         int npts, int N, Terrain T, float* __restrict__ measured) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)N * npts) return;
-  const int n = (int)(i / npts), p = (int)(i - (int64_t)n * npts);
-  if (T.type == 0) {  // plane (legged_robot.py:1564-1565)
-    measured[i] = 0.0f;
-    return;
-  }
-  const float* r = root + (size_t)n * 13;
+// one point of the scan: r = a base pose row (pos, quat xyzw: root_states[n] or body 0 of rigid_state[n]), (px, py) the
+// base-frame point.  The one statement of the chain, shared by k_measure_heights and k_height_scan.
+__device__ __forceinline__ float measure_height_point(const float* __restrict__ r, float px, float py, const Terrain& T) {
+  if (T.type == 0) return 0.0f;  // plane (legged_robot.py:1564-1565)
   // normalize((0, 0, qz, qw)) with the norm clamped at 1e-9 (torch_utils.normalize)
   float qz = r[5], qw = r[6];
   const float nrm = fmaxf(__fsqrt_rn(__fadd_rn(__fmul_rn(qz, qz), __fmul_rn(qw, qw))), 1e-9f);
   qz = __fdiv_rn(qz, nrm);
   qw = __fdiv_rn(qw, nrm);
   // quat_apply(q, v), v = (px, py, 0): t = 2 (q_xyz x v); v + w t + q_xyz x t
-  const float px = pts[2 * p], py = pts[2 * p + 1];
   const float tx = __fmul_rn(-__fmul_rn(qz, py), 2.0f), ty = __fmul_rn(__fmul_rn(qz, px), 2.0f);
   float x = __fadd_rn(__fadd_rn(px, __fmul_rn(qw, tx)), -__fmul_rn(qz, ty));
   float y = __fadd_rn(__fadd_rn(py, __fmul_rn(qw, ty)), __fmul_rn(qz, tx));
@@ -302,7 +296,22 @@ __global__ __launch_bounds__(256) void k_measure_heights(const float* __restrict
   iy = min(max(iy, 0), T.cols - 2);
   const int16_t* h = T.h + (size_t)ix * T.cols + iy;
   const int hm = min(min((int)h[0], (int)h[T.cols]), (int)h[1]);
-  measured[i] = __fmul_rn((float)hm, T.vscale);
+  return __fmul_rn((float)hm, T.vscale);
+}
+
+// the newest heights frame's entry (t1_dh_stand_env.py:466-468): clip(root_z - 0.5 - measured, -1, 1) * scale, clipped
+// to +-clip_obs
+__device__ __forceinline__ float critic_height_value(float root_z, float measured, float scale, float clip_obs) {
+  const float d = __fadd_rn(__fadd_rn(root_z, -0.5f), -measured);
+  return fminf(fmaxf(__fmul_rn(fminf(fmaxf(d, -1.0f), 1.0f), scale), -clip_obs), clip_obs);
+}
+
+__global__ __launch_bounds__(256) void k_measure_heights(const float* __restrict__ root, const float* __restrict__ pts,
+                                                         int npts, int N, Terrain T, float* __restrict__ measured) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)N * npts) return;
+  const int n = (int)(i / npts), p = (int)(i - (int64_t)n * npts);
+  measured[i] = measure_height_point(root + (size_t)n * 13, pts[2 * p], pts[2 * p + 1], T);
 }
 
 __global__ __launch_bounds__(256) void k_critic_heights(const float* __restrict__ priv, const float* __restrict__ root,
@@ -321,10 +330,141 @@ __global__ __launch_bounds__(256) void k_critic_heights(const float* __restrict_
   } else if (f < T1_CHIST - 1) {  // older frames: shifted by one, cleared for envs reset this step
     v = reset[n] ? 0.0f : prev[(size_t)n * RW + (f + 1) * W + k];
   } else {
-    const float d = __fadd_rn(__fadd_rn(root[(size_t)n * 13 + 2], -0.5f), -measured[(size_t)n * npts + (k - T1_NPRIV)]);
-    v = fminf(fmaxf(__fmul_rn(fminf(fmaxf(d, -1.0f), 1.0f), scale), -clip_obs), clip_obs);
+    v = critic_height_value(root[(size_t)n * 13 + 2], measured[(size_t)n * npts + (k - T1_NPRIV)], scale, clip_obs);
   }
   out[i] = v;
+}
+
+// -----------------------------------------------------------------------------------------------------
+// k_height_scan: the scan and the critic-history assembly as ONE launch after the step (t1env_height_scan).  The step
+// kernels report the post-physics root row to root_states[n] and to body 0 of rigid_state[n] alike (leg_report_rigid,
+// t1env_fused.h) and nothing after physics writes rigid_state, so after a real-dynamics step rigid_state[n, 0, 0:7] still
+// is the pre-reset pose the reference's callback samples, while root_states[n, 2] is the post-reset height the newest
+// heights frame reads.
+//
+// A workgroup owns a tile of TE consecutive envs (TE even): their rows of out (N, 3, 73 + npts) are contiguous, so it
+// assembles them in LDS and stores the tile as one stream, 16 bytes per lane.  E = the element's bits (uint32_t: fp32
+// histories, uint16_t: fp16): copied values pass through as bits, the newest frame is computed in fp32 and rounded
+// once.  With npts = 187 a row is 3120 B (fp32) or 1560 B (fp16): an even tile starts 16-byte aligned in both.  For any
+// other start (an odd npts, a caller's offset pointer) the LDS image is laid out `mis` elements in, so that 16-byte
+// chunks line up in LDS and in memory, and the chunks that straddle the tile's ends go element by element (fp16: by
+// 32-bit pairs where both halves are the tile's).  The sources -- the tile's priv rows (contiguous) and each env's two
+// older heights frames of prev -- are read the same way: the aligned 16-byte chunks inside a span as vectors, its ends
+// by element.  The int16 samples are a gather from a read-mostly field.
+// Per env-step at npts = 187: reads 876 + 1496 + 33 B (fp16: 438 + 748 + 33 B) and the samples, writes 3120 + 748 B
+// (fp16: 1560 + 748 B) -- tools/height_scan_timing.py keeps the count.
+// -----------------------------------------------------------------------------------------------------
+template <typename E> __device__ __forceinline__ E hs_bits(float v);
+template <> __device__ __forceinline__ uint32_t hs_bits<uint32_t>(float v) { return __float_as_uint(v); }
+template <> __device__ __forceinline__ uint16_t hs_bits<uint16_t>(float v) {
+  return __builtin_bit_cast(uint16_t, (_Float16)v);  // round to nearest even
+}
+
+// chunk c of the span [src, src + cnt): its aligned 16 bytes as one vector load where they lie inside the span, else
+// the elements that do; put(index in the span, bits)
+template <typename E, typename F>
+__device__ __forceinline__ void hs_load_chunk(const E* __restrict__ src, int cnt, int mis, int c, F&& put) {
+  constexpr int VE = 16 / (int)sizeof(E);
+  const int lo = c * VE - mis;
+  if (lo >= 0 && lo + VE <= cnt) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(src + lo);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < VE; ++j) {
+      if constexpr (sizeof(E) == 4) put(lo + j, (E)w[j]);
+      else put(lo + j, (E)(w[j / 2] >> (16 * (j & 1))));
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < VE; ++j)
+      if (lo + j >= 0 && lo + j < cnt) put(lo + j, src[lo + j]);
+  }
+}
+template <typename E> __device__ __forceinline__ int hs_misalign(const E* p) {
+  return (int)((reinterpret_cast<uintptr_t>(p) & 15) / sizeof(E));
+}
+template <typename E> __device__ __forceinline__ int hs_chunks(int mis, int cnt) {
+  constexpr int VE = 16 / (int)sizeof(E);
+  return (mis + cnt + VE - 1) / VE;
+}
+
+template <typename E>
+__global__ __launch_bounds__(256) void k_height_scan(const E* __restrict__ priv, const float* __restrict__ rigid,
+                                                     const float* __restrict__ root, const uint8_t* __restrict__ reset,
+                                                     const float* __restrict__ pts, const E* __restrict__ prev,
+                                                     E* __restrict__ out, float* __restrict__ measured, int npts, int N,
+                                                     int TE, Terrain T, float scale, float clip_obs) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char hs_lds[];
+  constexpr int VE = 16 / (int)sizeof(E), PRW = T1_NPRIV * T1_CHIST;
+  const int W = T1_NPRIV + npts, RW = T1_CHIST * W;
+  const int n0 = blockIdx.x * TE, ne = min(TE, N - n0), tid = threadIdx.x;
+  E* const dst = out + (size_t)n0 * RW;
+  const int mis = hs_misalign(dst), cnt = ne * RW;
+  E* const img = reinterpret_cast<E*>(hs_lds);  // 16-byte chunks of memory <-> of LDS
+  E* const tile = img + mis;                    // tile[e * RW + c]: column c of env n0 + e
+
+  // the 73-wide columns: the tile's priv rows are one contiguous span
+  {
+    const E* src = priv + (size_t)n0 * PRW;
+    const int pm = hs_misalign(src), nch = hs_chunks<E>(pm, ne * PRW);
+    for (int c = tid; c < nch; c += 256)
+      hs_load_chunk(src, ne * PRW, pm, c, [&](int i, E x) {
+        const int e = i / PRW, r = i - e * PRW, f = r / T1_NPRIV;
+        tile[e * RW + f * W + (r - f * T1_NPRIV)] = x;
+      });
+  }
+  // heights frames 0-1 = prev's frames 1-2, zero for an env reset this step: 2 spans of npts per env, CH chunk slots each
+  {
+    const int CH = (npts + VE - 1) / VE + 1;
+    for (int j = tid; j < ne * 2 * CH; j += 256) {
+      const int run = j / CH, c = j - run * CH, e = run >> 1, f = run & 1;
+      E* const d = tile + e * RW + f * W + T1_NPRIV;
+      const E* src = prev + (size_t)(n0 + e) * RW + (f + 1) * W + T1_NPRIV;
+      const int pm = hs_misalign(src);
+      if (c >= hs_chunks<E>(pm, npts)) continue;
+      if (reset[n0 + e]) {
+#pragma unroll
+        for (int k = 0; k < VE; ++k)
+          if (c * VE - pm + k >= 0 && c * VE - pm + k < npts) d[c * VE - pm + k] = (E)0;
+      } else {
+        hs_load_chunk(src, npts, pm, c, [&](int i, E x) { d[i] = x; });
+      }
+    }
+  }
+  // the scan from the pre-reset pose, and the newest heights frame from it and the post-reset height
+  for (int i = tid; i < ne * npts; i += 256) {
+    const int e = i / npts, p = i - e * npts, n = n0 + e;
+    const float m = measure_height_point(rigid + (size_t)n * (T1_NB * 13), pts[2 * p], pts[2 * p + 1], T);
+    measured[(size_t)n0 * npts + i] = m;
+    tile[e * RW + (T1_CHIST - 1) * W + T1_NPRIV + p] = hs_bits<E>(critic_height_value(root[(size_t)n * 13 + 2], m, scale, clip_obs));
+  }
+  __syncthreads();
+  // the tile as one stream: 16 bytes per lane; the chunks across its ends by element
+  E* const a = dst - mis;
+  const int nch = hs_chunks<E>(mis, cnt);
+  for (int c = tid; c < nch; c += 256) {
+    const int lo = c * VE - mis;
+    const u32x4 v = *reinterpret_cast<const u32x4*>(img + c * VE);
+    if (lo >= 0 && lo + VE <= cnt) {
+      *reinterpret_cast<u32x4*>(a + (size_t)c * VE) = v;
+      continue;
+    }
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if constexpr (sizeof(E) == 4) {
+        if (lo + q >= 0 && lo + q < cnt) dst[lo + q] = (E)w[q];
+      } else {
+        const int i0 = lo + 2 * q;
+        if (i0 >= 0 && i0 + 1 < cnt) {
+          *reinterpret_cast<uint32_t*>(dst + i0) = w[q];  // 4-byte aligned: an even offset from a 16-byte boundary
+        } else {
+          if (i0 >= 0 && i0 < cnt) dst[i0] = (E)(w[q] & 0xffffu);
+          if (i0 + 1 >= 0 && i0 + 1 < cnt) dst[i0 + 1] = (E)(w[q] >> 16);
+        }
+      }
+    }
+  }
 }
 
 // creation-time state (see t1env_init in include/t1env.h)
@@ -720,6 +860,39 @@ int t1env_critic_heights(t1env* e, int32_t obs_slot, int32_t npts, float scale, 
   hipLaunchKernelGGL(k_critic_heights, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      e->buf.priv_buf[obs_slot], e->buf.root_states, e->buf.reset_buf, measured, prev, out, npts, N,
                      scale, e->cfg.clip_obs);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int t1env_height_scan(t1env* e, int32_t obs_slot, const float* points, int32_t npts, float scale, float* measured,
+                      const void* prev, void* out, void* stream) {
+  if (!e || !points || !measured || !prev || !out || npts <= 0 || (obs_slot & ~1))
+    return fail(T1ENV_E_ARG, "t1env_height_scan: bad argument");
+  const bool half = e->cfg.obs_half != 0;
+  const size_t es = half ? 2 : 4;
+  if (prev == out || ((uintptr_t)prev | (uintptr_t)out) % es != 0)
+    return fail(T1ENV_E_ARG, "t1env_height_scan: prev and out must be two buffers of the history's element type");
+  if (e->terrain.type != 0 && !e->terrain.h) return fail(T1ENV_E_STATE, "t1env_height_scan: no terrain set");
+  // the largest even tile of envs whose rows (and the alignment slack) fit 64 KB of LDS: 8 at npts = 187
+  const size_t row = (size_t)T1_CHIST * (T1_NPRIV + (size_t)npts) * es;
+  int te = 8;
+  while (te > 0 && te * row + 32 > 64 * 1024) te -= 2;
+  if (te <= 0) return fail(T1ENV_E_ARG, "t1env_height_scan: npts too large for one workgroup's tile");
+  const int N = e->cfg.num_envs;
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 g((unsigned)grid(N, te)), b(256);
+  const size_t lds = te * row + 32;
+  const t1env_buffers& B = e->buf;
+  const int t = t_begin(e, 4, s);
+  if (half)
+    hipLaunchKernelGGL(k_height_scan<uint16_t>, g, b, lds, s, reinterpret_cast<const uint16_t*>(B.priv_buf[obs_slot]),
+                       B.rigid_state, B.root_states, B.reset_buf, points, static_cast<const uint16_t*>(prev),
+                       static_cast<uint16_t*>(out), measured, npts, N, te, e->terrain, scale, e->cfg.clip_obs);
+  else
+    hipLaunchKernelGGL(k_height_scan<uint32_t>, g, b, lds, s, reinterpret_cast<const uint32_t*>(B.priv_buf[obs_slot]),
+                       B.rigid_state, B.root_states, B.reset_buf, points, static_cast<const uint32_t*>(prev),
+                       static_cast<uint32_t*>(out), measured, npts, N, te, e->terrain, scale, e->cfg.clip_obs);
+  t_end(e, t, s);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -214,15 +214,13 @@ class T1DHStandEnv(VecEnv):
         if (self.num_single_obs, e.single_num_privileged_obs, e.frame_stack, e.c_frame_stack, self.num_actions) != \
                 (_lib.NOBS, _lib.NPRIV, _lib.HIST, _lib.CHIST, _lib.ND):
             raise ValueError("the HIP kernels are specialised for the t1_dh_stand layout (47 x 66 obs, 73 x 3 priv)")
-        # height scan (inactive in DHT1StandCfg): 187 heights per critic frame, t1env_measure_heights /
-        # t1env_critic_heights between and after the split step phases
+        # height scan (inactive in DHT1StandCfg): 187 heights per critic frame, one t1env_height_scan launch after
+        # the step (fp32 or fp16 histories)
         self.measure_heights = bool(cfg.terrain.measure_heights)
         sd = getattr(cfg.env, "state_dtype", "fp32")
         if sd not in ("fp32", "fp16"):
             raise ValueError(f"cfg.env.state_dtype must be 'fp32' or 'fp16', got {sd!r}")
         self.obs_dtype = torch.float16 if sd == "fp16" else torch.float32
-        if self.obs_dtype == torch.float16 and self.measure_heights:
-            raise NotImplementedError("fp16 histories (state_dtype='fp16') with measure_heights=True")
         self.env_offset = int(env_offset)
         self.num_envs_total = int(num_envs_total) if num_envs_total is not None else N
         self.dt = cfg.control.decimation * self.sim_params.dt
@@ -324,7 +322,7 @@ class T1DHStandEnv(VecEnv):
             self.height_points[:, :, :2] = self._height_pts
             self.measured_heights = z(N, self.num_height_points)
             w = self.cfg.env.c_frame_stack * (self.cfg.env.single_num_privileged_obs + self.num_height_points)
-            self._priv_ext = [z(N, w), z(N, w)]
+            self._priv_ext = [z(N, w, dtype=h), z(N, w, dtype=h)]   # measured_heights stays fp32
 
     def _build_model(self, urdf_path):
         cfg = self.cfg
@@ -590,7 +588,13 @@ class T1DHStandEnv(VecEnv):
         a = self._args(self.common_step_counter, ext_call, ext_first, push_call)
         ctr_post = self.common_step_counter + 1
         needs_curriculum = self.cfg.commands.curriculum and ctr_post % self.max_episode_length == 0
-        if _injected is None and not needs_curriculum and not self.measure_heights:
+        # the height scan of an injected step samples root_states between the phases (its rigid rows are synthetic);
+        # a real-dynamics step leaves the pre-reset pose in rigid_state, and one launch after the step scans it
+        split_scan = self.measure_heights and _injected is not None
+        if split_scan and self.obs_dtype == torch.float16:
+            raise NotImplementedError("injected physics with fp16 histories (state_dtype='fp16') and "
+                                      "measure_heights=True: the split height scan is fp32 only")
+        if _injected is None and not needs_curriculum:
             _lib.check(lib.t1env_step(h, _ptr(actions), _lib.C.byref(a), s), "t1env_step")
         else:
             if _injected is None:
@@ -598,7 +602,7 @@ class T1DHStandEnv(VecEnv):
             else:
                 _lib.check(lib.t1env_step_injected(h, _ptr(actions), _lib.C.byref(a), _lib.C.byref(_injected), s),
                            "t1env_step_injected")
-            if self.measure_heights:   # the callback's _get_heights, before reset_idx (t1_dh_stand_env.py:190)
+            if split_scan:   # the callback's _get_heights, before reset_idx (t1_dh_stand_env.py:190)
                 _lib.check(lib.t1env_measure_heights(h, _ptr(self._height_pts), self.num_height_points,
                                                      _ptr(self.measured_heights), s), "t1env_measure_heights")
             if needs_curriculum:
@@ -607,11 +611,16 @@ class T1DHStandEnv(VecEnv):
                 self._command_curriculum(float(acc[idx]), float(acc[_lib.ACC_COUNT]))
                 a = self._args(self.common_step_counter, ext_call, ext_first, push_call)
             _lib.check(lib.t1env_step_reset_and_observe(h, _lib.C.byref(a), s), "t1env_step_reset_and_observe")
-            if self.measure_heights:
+            if split_scan:
                 _lib.check(lib.t1env_critic_heights(h, self._slot, self.num_height_points,
                                                     float(self.obs_scales.height_measurements),
                                                     _ptr(self.measured_heights), _ptr(self._priv_ext[self._slot ^ 1]),
                                                     _ptr(self._priv_ext[self._slot]), s), "t1env_critic_heights")
+        if self.measure_heights and not split_scan:
+            _lib.check(lib.t1env_height_scan(h, self._slot, _ptr(self._height_pts), self.num_height_points,
+                                             float(self.obs_scales.height_measurements), _ptr(self.measured_heights),
+                                             _ptr(self._priv_ext[self._slot ^ 1]), _ptr(self._priv_ext[self._slot]), s),
+                       "t1env_height_scan")
         self.common_step_counter += 1
         self._slot ^= 1
         self._fill_extras(self.common_step_counter % EXTRAS_RING)
@@ -681,8 +690,8 @@ class T1DHStandEnv(VecEnv):
     def set_substep_log(self, enable=True):
         """Test hook (t1env_set_substep_log): every following fused step also writes its per-substep root / dof
         states and torques to ``self.substep_log`` = dict(root (dec, N, 13), dof (dec, N, 12, 2), torque (dec, N, 12)),
-        the states the reference's post-simulate code would see.  Split steps (command curriculum, height scan)
-        raise while it is on."""
+        the states the reference's post-simulate code would see.  Split steps (command curriculum) raise while it
+        is on."""
         if not enable:
             _lib.check(self._lib.t1env_set_substep_log(self._handle, None), "t1env_set_substep_log")
             self.substep_log = None
@@ -701,7 +710,7 @@ class T1DHStandEnv(VecEnv):
         _lib.check(self._lib.t1env_set_timing(self._handle, int(enable) | (0 if reset else 2)), "t1env_set_timing")
 
     def get_timing(self):
-        names = ["k_dynamics", "k_post_a", "k_post_b", "k_shift", "unused", "step"]  # include/t1env.h timers
+        names = ["k_dynamics", "k_post_a", "k_post_b", "k_shift", "k_height_scan", "step"]  # include/t1env.h timers
         ms = (_lib.C.c_double * len(names))()
         n = (_lib.C.c_int32 * len(names))()
         _lib.check(self._lib.t1env_get_timing(self._handle, ms, n), "t1env_get_timing")
