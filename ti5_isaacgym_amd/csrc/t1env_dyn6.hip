@@ -92,8 +92,9 @@ __device__ unsigned long long g_t1_wgsum6[4096][T1_WGSUM6_N];
 // wave): [0] past the epilogue barrier, [1] post_a_core done, [2] its reset-row work issued, [3] its stores drained
 // (arrival at E2), [4] past E2, [5] the finaliser done.  W1 (the state wave): [8] past the epilogue barrier,
 // [9] post_a_core done, [10] its reset work ahead of E2 done, [11] the level sum stored and drained (arrival at E2),
-// [12] past E2, [13] its end
-constexpr int T1_TAIL6_N = 16;
+// [12] past E2, [13] its end.  The dealt reward pass: W0 [6] its own terms done (arrival at the hand-over word), [7] past
+// its wait there; [14] - [17] the arrival there of the helpers W4 - W7 (10 + wave)
+constexpr int T1_TAIL6_N = 20;
 __device__ unsigned long long g_t1_tail6[4096][T1_TAIL6_N];
 #define T1_CLOCK_STAMP(k)                                                          \
   if ((threadIdx.x & 63) == 0 && blockIdx.x < 4096)                                \
@@ -162,7 +163,27 @@ struct Dyn6Lds {
   float rtf[2][3][64];    // the report: terrain forces on the shank [0] (W2) / foot [1] (W3)
   float rsf[2][3][64];    // the report: self-contact forces on the shank / foot (W5)
   uint32_t e2;            // the epilogue's E2 flag: W1's terrain-level sum is stored (W1 -> W0)
+  uint32_t rwn;           // the reward helpers that are done (W4-W7 -> W0), zeroed and polled as e2
+  float rw[T1_NREW][NE6];  // the helpers' unscaled reward terms (W4-W7 -> W0)
 };
+// The reward terms the helper waves evaluate for W0 after the epilogue barrier (the rest, the ordered sum and every
+// store are W0's).  W4: the terms on the base quantities; W5-W7 ahead of their share of the reset rows: W5 the joint-position terms
+// (they read the callback's commands and push), W6 the joint-velocity, torque and action terms (no prefix at all), W7
+// the stateless terms on the feet and knees.  W0 keeps the terms that advance state (feet_air_time, feet_clearance),
+// those on the feet's Euler angles, which it stores, and the cheap contact terms.
+constexpr uint32_t REW6_W4 = (1u << T1_REW_LOW_SPEED) | (1u << T1_REW_ORIENTATION) | (1u << T1_REW_TRACK_VEL_HARD) |
+                             (1u << T1_REW_TRACKING_ANG_VEL) | (1u << T1_REW_TRACKING_LIN_VEL) |
+                             (1u << T1_REW_VEL_MISMATCH_EXP);
+constexpr uint32_t REW6_W5 = (1u << T1_REW_BASE_ACC) | (1u << T1_REW_DEFAULT_JOINT_POS) | (1u << T1_REW_JOINT_POS) |
+                             (1u << T1_REW_DOF_VEL_LIMITS) | (1u << T1_REW_STAND_SYSMETRY);
+constexpr uint32_t REW6_W6 = (1u << T1_REW_ACTION_SMOOTHNESS) | (1u << T1_REW_DOF_ACC) | (1u << T1_REW_DOF_VEL) |
+                             (1u << T1_REW_TORQUES);
+constexpr uint32_t REW6_W7 = (1u << T1_REW_FEET_DISTANCE) | (1u << T1_REW_KNEE_DISTANCE) | (1u << T1_REW_FOOT_SLIP) |
+                             (1u << T1_REW_FEET_CONTACT_FORCES);
+constexpr uint32_t REW6_HELPED = REW6_W4 | REW6_W5 | REW6_W6 | REW6_W7;
+constexpr uint32_t REW6_HELPERS = 4;
+static_assert(__builtin_popcount(REW6_HELPED) == __builtin_popcount(REW6_W4) + __builtin_popcount(REW6_W5) +
+              __builtin_popcount(REW6_W6) + __builtin_popcount(REW6_W7), "a term has one owner");
 T1_ROWS_ALIGNED(Dyn6Lds, st);
 T1_ROWS_ALIGNED(Dyn6Lds, wb);
 T1_ROWS_ALIGNED(Dyn6Lds, sj);
@@ -769,7 +790,12 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
       if constexpr (FUSED) { lds.fr[F_CFB][e] = fb.x; lds.fr[F_CFB + 1][e] = fb.y; lds.fr[F_CFB + 2][e] = fb.z; }
     }
     T1_PROF_MARK(10);
-    if constexpr (FUSED) __syncthreads();  // the epilogue barrier
+    if constexpr (FUSED) {
+      __syncthreads();  // the epilogue barrier
+      // W4 has no other part in the epilogue: its share of the reward terms, handed to W0 in LDS
+      fused_epilogue_staged<POST_A_REW_HELPER, NE6, true, /*RESET_ROWS=*/false, REW6_W4>(
+          M, C, B, A, S, FA, dyn_blocks, lane, lds.epi, lds.fr, lds.act, lds.act + NLEG, nullptr, lds.rw, &lds.rwn);
+    }
     T1_CLOCK_WAVE_END();
     T1_PROF_END();
     return;
@@ -988,7 +1014,7 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
       }
     }
     if constexpr (FUSED) {
-      if (role == 1 && lane == 0) lds.e2 = 0u;
+      if (role == 1 && lane == 0) { lds.e2 = 0u; lds.rwn = 0u; }
       __syncthreads();  // the epilogue barrier: every output of the workgroup is in LDS / memory
       T1_PROF_MARK(12);
       if (role == 1)
@@ -998,10 +1024,21 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
         fused_epilogue_obs<POST_OBS_PRIV, NE6>(M, C, B, A, lane, lds.epi, lds.fr, lds.act, lds.act + NLEG);
       else if (role == 3)
         fused_epilogue_obs<POST_OBS_ACTOR, NE6>(M, C, B, A, lane, lds.epi, lds.fr, lds.act, lds.act + NLEG);
-      else if (wave >= 5)  // W5-W7 have no part in the epilogue: they zero the reset envs' history rows between them
-        // (not W4: the shift's arguments kept live to the end of its branch cost the <HF, FUSED> build two more
-        // spilled VGPRs)
+      else if (wave >= 5) {  // W5-W7: each its share of the reward terms first (W0 waits for them), then the reset
+        // envs' history rows zeroed between them (nothing waits for the zeroing)
+        if (role == 5)
+          fused_epilogue_staged<POST_A_REW_HELPER, NE6, true, /*RESET_ROWS=*/false, REW6_W5>(
+              M, C, B, A, S, FA, dyn_blocks, lane, lds.epi, lds.fr, lds.act, lds.act + NLEG, nullptr, lds.rw, &lds.rwn);
+        else if (role == 6)
+          fused_epilogue_staged<POST_A_REW_HELPER, NE6, true, /*RESET_ROWS=*/false, REW6_W6>(
+              M, C, B, A, S, FA, dyn_blocks, lane, lds.epi, lds.fr, lds.act, lds.act + NLEG, nullptr, lds.rw, &lds.rwn);
+        else
+          fused_epilogue_staged<POST_A_REW_HELPER, NE6, true, /*RESET_ROWS=*/false, REW6_W7>(
+              M, C, B, A, S, FA, dyn_blocks, lane, lds.epi, lds.fr, lds.act, lds.act + NLEG, nullptr, lds.rw, &lds.rwn);
+        // (W4 takes no part in the zeroing: the shift's arguments kept live to the end of its branch cost the
+        // <HF, FUSED> build two more spilled VGPRs)
         epilogue_zero_reset_rows<NE6>(C, B, S, lane, (int)threadIdx.x - 320, 192, lds.epi, lds.fr);
+      }
       T1_PROF_MARK(15);
     }
     T1_CLOCK_WAVE_END();
@@ -1173,8 +1210,9 @@ __global__ __launch_bounds__(D6_BLOCK) void k_dyn6(const DynModel* __restrict__ 
   if constexpr (FUSED) {
     __syncthreads();  // the epilogue barrier: every output of the workgroup is in LDS / memory
     T1_PROF_MARK(12);
-    fused_epilogue_staged<POST_A_REWARDS, NE6, true, /*RESET_ROWS=*/false>(M, C, B, A, S, FA, dyn_blocks, lane, lds.epi,
-                                                                           lds.fr, lds.act, lds.act + NLEG, &lds.e2);
+    fused_epilogue_staged<POST_A_REWARDS, NE6, true, /*RESET_ROWS=*/false, REW_ALL & ~REW6_HELPED>(
+        M, C, B, A, S, FA, dyn_blocks, lane, lds.epi, lds.fr, lds.act, lds.act + NLEG, &lds.e2, lds.rw, &lds.rwn,
+        REW6_HELPERS);
   }
   T1_CLOCK_END();
   T1_PROF_END();

@@ -346,6 +346,92 @@ __device__ __forceinline__ void epilogue_reset_rest(const DynModel& M, const t1e
   if (resample_commands_r(C, A, O.el, O.gt, O.cmd, genv, ctr)) strow(B.commands + n * 4, O.cmd);
 }
 
+// element i of a register row, by selects (a runtime register index would go to scratch).  The chain opens on a
+// constant, not on v[0]: a select between two elements of the row becomes a load through a selected pointer before the
+// row is split into registers, and the row stays in scratch after all.
+template <int K, typename T>
+__device__ __forceinline__ T row_sel(const T (&v)[K], int i) {
+  T r = T(0);
+#pragma unroll
+  for (int k = 0; k < K; ++k) r = i == k ? v[k] : r;
+  return r;
+}
+
+// epilogue_reset_rest of one env by a whole wave (k_dyn6's state wave behind the E2 flag): every argument but `lane` is
+// wave-uniform, and lane i takes element i of each row it stores, so a row costs one store instruction and the 72
+// domain-randomisation draws two passes over the wave instead of 72 one-lane draws.  Every draw is counter-based, so a
+// lane draws its own element from (K, slot); each stored value is reset_env_rest's expression for that element (the
+// one-lane form stays the split kernels', k_dyn5's, k_dyn4's and the E2-as-barrier path's, and the tests' reference).
+// As there with zero_reward_state = false, obs_elsewhere = true, zero_lag_rings = false: the reward state is the
+// rewards wave's, the last_* rows the observation waves', the lag rings W5-W7's (epilogue_zero_reset_rows).
+__device__ __forceinline__ void epilogue_reset_rest_wide(const DynModel& M, const t1env_config& C,
+                                                         const t1env_buffers& B, const t1env_step_args& A, int n,
+                                                         uint32_t genv, uint32_t ctr, RngKey K, const float (&cmd)[4],
+                                                         const float (&org)[3], int lane) {
+  // the scalars, the gait times, the base quantities and the redrawn commands: evaluated on every lane (the cost of
+  // one), stored an element per lane
+  ObsIn R;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) R.cmd[i] = cmd[i];
+  reset_obs_inputs(M, C, K, R, /*dof=*/false);
+  const bool cmd_dirty = resample_commands_r(C, A, R.el, R.gt, R.cmd, genv, ctr);
+  if (lane < NVIMP) B.contact_vimp[(size_t)n * NVIMP + lane] = 0.0f;
+  if (lane < 24) {  // _reset_dofs: word 2 j the position of joint j, word 2 j + 1 its velocity
+    const int j = lane >> 1;
+    const float q = M.default_dof_pos[j] + rand_float(-C.reset_dof_range, C.reset_dof_range, K, SLOT_RESET_DOF + j);
+    B.dof_state[n * 24 + lane] = (lane & 1) ? 0.0f : q;
+  }
+  if (lane < 13) {  // _reset_root_states
+    float r = M.base_init_state[lane];
+    if (lane < 3) r += row_sel(org, lane);
+    if (C.custom_origins && lane < 2) {
+      const float p3 = C.reset_xy_range;
+      r += rand_float(-p3, p3, K, SLOT_RESET_ROOT_XY + lane);
+    }
+    B.root_states[n * 13 + lane] = r;
+  }
+  // randomize_dof_props: element i = 12 a + j is joint j of array a (offsets, kp, kd, coulomb, viscous, armature)
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const int i = lane + 64 * p;
+    if (i < 72) {
+      const int a = i / 12, j = i - 12 * a;
+      const float lo = a == 0 ? C.motor_offset_range[0] : a == 1 ? C.kp_mult_range[0] : a == 2 ? C.kd_mult_range[0]
+                     : a == 3 ? C.coulomb_range[0] : a == 4 ? C.viscous_range[0] : C.armature_range[j][0];
+      const float hi = a == 0 ? C.motor_offset_range[1] : a == 1 ? C.kp_mult_range[1] : a == 2 ? C.kd_mult_range[1]
+                     : a == 3 ? C.coulomb_range[1] : a == 4 ? C.viscous_range[1] : C.armature_range[j][1];
+      const uint32_t slot = a == 0 ? SLOT_DR_OFFSET : a == 1 ? SLOT_DR_KP : a == 2 ? SLOT_DR_KD
+                          : a == 3 ? SLOT_DR_COULOMB : a == 4 ? SLOT_DR_VISCOUS : SLOT_DR_ARMATURE;
+      // (armature_shared: every joint takes joint 0's draw, as in reset_env_rest)
+      const float u = rand_float(lo, hi, K, slot + (a == 5 && C.armature_shared ? 0 : j));
+      const float v = a == 1 ? u * M.p_gains[j] : a == 2 ? u * M.d_gains[j] : u;
+      float* const dst = a == 0 ? B.motor_offsets : a == 1 ? B.kp : a == 2 ? B.kd
+                       : a == 3 ? B.coulomb : a == 4 ? B.viscous : B.armature;
+      dst[n * 12 + j] = v;
+    }
+  }
+  // randomize_lag_props' lag lengths, the buffers
+  if (lane < 12) B.actions[n * 12 + lane] = 0.0f;
+  if (lane < 3) {
+    B.gait_time[n * 3 + lane] = row_sel(R.gt, lane);
+    // base quantities of the reset env from the fresh root state (t1:548-552)
+    B.base_lin_vel[n * 3 + lane] = row_sel(R.bq.lin, lane);
+    B.base_ang_vel[n * 3 + lane] = row_sel(R.bq.ang, lane);
+    B.projected_gravity[n * 3 + lane] = row_sel(R.bq.grav, lane);
+    B.base_euler_xyz[n * 3 + lane] = row_sel(R.bq.euler, lane);
+  }
+  if (lane == 0) {
+    if (cmd_dirty) strow(B.commands + n * 4, R.cmd);
+    B.lag_timestep[n] = rand_int(C.lag_range[0], C.lag_range[1] + 1, K, SLOT_LAG_ACTION);
+    B.dof_lag_timestep[n] = R.dl;
+    B.imu_lag_timestep[n] = R.il;
+    B.episode_length_buf[n] = 0;
+    B.phase_length_buf[n] = 0;
+    B.reset_buf[n] = 1;
+    B.gait_start[n] = R.gstart;
+  }
+}
+
 // The fused step's post-physics for the NE envs of one workgroup, run by four waves after the epilogue barrier (lane =
 // env; lanes >= NE shadow an env of the workgroup and store nothing), every input from LDS (fresh outputs FR, staged
 // state E, the clipped actions in ACT0 (joints 0-5) / ACT1 (joints 6-11)).  This function is the two post_a waves:
@@ -357,16 +443,19 @@ __device__ __forceinline__ void epilogue_reset_rest(const DynModel& M, const t1e
 // (epilogue_zero_reset_rows).
 // e2_flag (k_dyn6, with RESET_ROWS = false): E2 is a flag in LDS instead of a barrier.  The state wave sets it once its
 // level sum is stored and goes on; the rewards wave waits for it alone.  The flag is 0 before the epilogue barrier.
-template <int PART, int NE, bool INWG, bool RESET_ROWS = true>
+// TERMS, RW / rw_count / rw_helpers (k_dyn6): the reward terms are dealt over the rewards wave and helper waves that
+// idle in the epilogue (PART = POST_A_REW_HELPER: the prefix, its terms into RW, nothing stored); see post_a_core.
+template <int PART, int NE, bool INWG, bool RESET_ROWS = true, uint32_t TERMS = REW_ALL>
 __device__ __forceinline__ void fused_epilogue_staged(const DynModel& M, const t1env_config& C, const t1env_buffers& B,
                                                       const t1env_step_args& A, const ShiftArgs& S,
                                                       const FusedArgs& FA, int dyn_blocks, int lane,
                                                       const float (*E)[NE], const float (*FR)[NE],
                                                       const float (*ACT0)[NE], const float (*ACT1)[NE],
-                                                      uint32_t* e2_flag = nullptr) {
+                                                      uint32_t* e2_flag = nullptr, float (*RW)[NE] = nullptr,
+                                                      uint32_t* rw_count = nullptr, uint32_t rw_helpers = 0) {
   const int N = C.num_envs;
   constexpr int TS = PART == POST_A_REWARDS ? 0 : 8;  // this wave's tail stamps (a probe build's)
-  T1_CLOCK_STAMP(TS);
+  if constexpr (PART != POST_A_REW_HELPER) T1_CLOCK_STAMP(TS);
   const int e = lane % NE;  // the LDS column (lanes >= NE read a valid column and are inactive)
   const int n0 = lane < NE ? (int)blockIdx.x * NE + lane : N;
   const bool active = n0 < N;
@@ -417,7 +506,13 @@ __device__ __forceinline__ void fused_epilogue_staged(const DynModel& M, const t
   // the state wave's term of the terrain-level sum: the env's level as it stands, read ahead of post_a_core's stores
   const bool in_level_sum = PART == POST_A_STATE && C.custom_origins && active;
   int level = in_level_sum ? B.terrain_levels[n] : 0;
-  const bool do_reset = post_a_core<PART>(M, C, B, A, n0, X, bq, PART == POST_A_REWARDS ? ep_row : nullptr);
+  RewDeal D;
+  if (RW) {
+    D.rows = &RW[0][0]; D.stride = NE; D.col = e; D.owner = lane < NE;
+    D.count = rw_count; D.helpers = rw_helpers;
+  }
+  const bool do_reset = post_a_core<PART, TERMS>(M, C, B, A, n0, X, bq, PART == POST_A_REWARDS ? ep_row : nullptr, D);
+  if constexpr (PART == POST_A_REW_HELPER) return;
   T1_PROF_MARK(13);
   T1_CLOCK_STAMP(TS + 1);
   if constexpr (PART == POST_A_REWARDS) {
@@ -438,9 +533,10 @@ __device__ __forceinline__ void fused_epilogue_staged(const DynModel& M, const t
   }
   // reset_idx (post_b's first half) of the resetting envs, in two parts: the terrain curriculum, which settles the
   // terrain-level sum the rewards wave needs before it may enter the extras finaliser, and the rest of the new state
-  // (about 60 draws and 300 one-lane stores), the gait times and the redrawn commands, which nothing waits for but the
+  // (about 90 draws and 160 stored words), the gait times and the redrawn commands, which nothing waits for but the
   // end of the kernel.  With E2 as a flag the level sum is stored and signalled between the two and this wave never
-  // waits.  With E2 as a barrier the whole reset stays ahead of it: this wave would stand at the barrier until the
+  // waits, and it runs the rest with all its lanes on one resetting env at a time (epilogue_reset_rest_wide: a reset
+  // workgroup ends with this wave).  With E2 as a barrier the whole reset stays ahead of it: this wave would stand at the barrier until the
   // rewards wave's longer pass arrives and only then run the rest (measured slower).  The
   // observation waves take a resetting env's inputs from its draws, not from these rows.
   const uint32_t genv = (uint32_t)(C.env_offset + n);
@@ -465,8 +561,25 @@ __device__ __forceinline__ void fused_epilogue_staged(const DynModel& M, const t
     __syncthreads();
   }
   T1_CLOCK_STAMP(TS + 4);
-  if (e2_flag && active && do_reset)
-    epilogue_reset_rest(M, C, B, A, n, genv, ctr, K, X.cmd, org, org_known, /*zero_lag_rings=*/RESET_ROWS);
+  if (e2_flag) {  // the rest of the reset, wave-wide: one resetting env at a time, its lane's values broadcast (the
+                  // lag rings are not zeroed here: with the flag RESET_ROWS is false and they are W5-W7's)
+    if (active && do_reset && !org_known)  // (no curriculum: the env's origin as it stands)
+#pragma unroll
+      for (int i = 0; i < 3; ++i) org[i] = B.env_origins[n * 3 + i];
+    unsigned long long todo = __ballot(active && do_reset);
+    while (todo) {
+      const int l = __ffsll(todo) - 1;
+      todo &= todo - 1;
+      const int nl = (int)blockIdx.x * NE + l;
+      const RngKey Kl = {(uint32_t)__builtin_amdgcn_readlane((int)K.h, l)};
+      float cmd_l[4], org_l[3];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) cmd_l[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(X.cmd[i]), l));
+#pragma unroll
+      for (int i = 0; i < 3; ++i) org_l[i] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(org[i]), l));
+      epilogue_reset_rest_wide(M, C, B, A, nl, (uint32_t)(C.env_offset + nl), ctr, Kl, cmd_l, org_l, lane);
+    }
+  }
   T1_CLOCK_STAMP(TS + 5);
   T1_PROF_MARK(15);
 }

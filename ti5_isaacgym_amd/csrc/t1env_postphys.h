@@ -5,6 +5,11 @@
 #pragma once
 #include "t1env_device.h"
 
+// tail stamps of a -DT1_PROBE_CLOCK build of k_dyn6 (t1env_dyn6.hip defines it ahead of this header); nothing elsewhere
+#ifndef T1_CLOCK_STAMP
+#define T1_CLOCK_STAMP(k) ((void)0)
+#endif
+
 namespace t1 {
 
 // =====================================================================================================
@@ -272,11 +277,35 @@ __device__ __forceinline__ bool post_callback(const t1env_config& C, const t1env
 // state, extras sums) and zeroes the reward state of resetting envs itself; POST_A_STATE runs the same prefix
 // and the state-owned stores (counters, base quantities, commands, push, external force, reset / time-out
 // flags) for the wave that continues with post_b.  The prefix is deterministic, so both waves agree.
-enum : int { POST_A_ALL = 0, POST_A_REWARDS = 1, POST_A_STATE = 2, POST_OBS_PRIV = 3, POST_OBS_ACTOR = 4 };
-template <int PART = POST_A_ALL>
+// The reward pass dealt over several waves (k_dyn6): TERMS is the set of reward terms this wave evaluates (bit k = term
+// k).  PART = POST_A_REW_HELPER runs the prefix its terms read, evaluates them, writes each unscaled r[k] to its row
+// of D (LDS) and adds 1 to D.count with release order; it stores nothing else and returns.  POST_A_REWARDS with a
+// smaller set evaluates its own terms, waits until D.count equals D.helpers and takes the other terms' r[k] from D;
+// the ordered sum, the clip, the episode sums and every store stay with it.  r[k] is handed over, not r[k] * scale:
+// the sum is the same expression on the same values (no contraction in this file), so no bit moves.
+// A helper's terms keep no state and do not read the feet's Euler angles (the rewards wave stores both).
+enum : int { POST_A_ALL = 0, POST_A_REWARDS = 1, POST_A_STATE = 2, POST_OBS_PRIV = 3, POST_OBS_ACTOR = 4,
+             POST_A_REW_HELPER = 5 };
+constexpr uint32_t REW_ALL = (1u << T1_NREW) - 1u;
+constexpr uint32_t REW_HELPER_TERMS =
+    REW_ALL & ~((1u << T1_REW_FEET_AIR_TIME) | (1u << T1_REW_FEET_CLEARANCE) | (1u << T1_REW_FEET_ROTATION) |
+                (1u << T1_REW_STAND_STILL) | (1u << T1_REW_TERMINATION));
+constexpr bool rew_in(uint32_t terms, int k) { return ((terms >> k) & 1u) != 0u; }
+struct RewDeal {
+  float* rows = nullptr;      // [T1_NREW][stride] unscaled rewards, this lane's column at rows + col
+  int stride = 0, col = 0;
+  bool owner = false;         // a helper's lane that writes its column (one lane per env)
+  uint32_t* count = nullptr;  // helpers done (0 before the epilogue barrier)
+  uint32_t helpers = 0;
+};
+template <int PART = POST_A_ALL, uint32_t TERMS = REW_ALL>
 __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_config& C, const t1env_buffers& B,
                                             const t1env_step_args& A, int n0, PostAIn& X, BaseQ& bq,
-                                            float* ep_row = nullptr) {
+                                            float* ep_row = nullptr, const RewDeal D = RewDeal{}) {
+  static_assert(rew_in(TERMS, T1_REW_DOF_ACC) == rew_in(TERMS, T1_REW_DOF_VEL) &&
+                rew_in(TERMS, T1_REW_FEET_DISTANCE) == rew_in(TERMS, T1_REW_KNEE_DISTANCE), "evaluated in one block");
+  static_assert(PART == POST_A_REWARDS || PART == POST_A_REW_HELPER || TERMS == REW_ALL, "only the fused reward pass is dealt");
+  static_assert(PART != POST_A_REW_HELPER || (TERMS & ~REW_HELPER_TERMS) == 0u, "a helper's terms keep no state");
   const bool live = n0 < C.num_envs;
   const int n = live ? n0 : C.num_envs - 1;
   const uint32_t genv = (uint32_t)(C.env_offset + n);
@@ -319,7 +348,7 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
   const float* pg = bq.grav;
   const float* be = bq.euler;
   float fe[6];
-  if constexpr (PART != POST_A_STATE) {
+  if constexpr (PART != POST_A_STATE && PART != POST_A_REW_HELPER) {
     const float q0[4] = {f0[3], f0[4], f0[5], f0[6]}, q1[4] = {f1[3], f1[4], f1[5], f1[6]};
     euler_xyz(q0, fe);
     euler_xyz(q1, fe + 3);
@@ -341,7 +370,7 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
   const bool contact0 = c0[2] > 5.0f, contact1 = c1[2] > 5.0f;
   float r[T1_NREW];
   if constexpr (PART != POST_A_STATE) {
-    {  // action_smoothness
+    if constexpr (rew_in(TERMS, T1_REW_ACTION_SMOOTHNESS)) {  // action_smoothness
       float t1s = 0.0f, t2s = 0.0f, t3s = 0.0f;
 #pragma unroll
       for (int j = 0; j < 12; ++j) {
@@ -353,19 +382,19 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
       }
       r[T1_REW_ACTION_SMOOTHNESS] = (t1s + t2s) + 0.05f * t3s;
     }
-    {  // base_acc (root velocity after a push, like the reference's root_states)
+    if constexpr (rew_in(TERMS, T1_REW_BASE_ACC)) {  // base_acc (root velocity after a push, like the reference's root_states)
       float s = 0.0f;
 #pragma unroll
       for (int i = 0; i < 6; ++i) { const float d = lrv[i] - root[7 + i]; s += d * d; }
       r[T1_REW_BASE_ACC] = expf(-sqrtf(s) * 3.0f);
     }
-    {  // base_height
+    if constexpr (rew_in(TERMS, T1_REW_BASE_HEIGHT)) {  // base_height
       const float mh = (f0[2] * ph.stance[0] + f1[2] * ph.stance[1]) / (ph.stance[0] + ph.stance[1]);
       const float bh = root[2] - (mh - 0.05f);
       r[T1_REW_BASE_HEIGHT] = expf(-fabsf(bh - C.base_height_target) * 100.0f);
     }
-    r[T1_REW_COLLISION] = norm3(cfb[0], cfb[1], cfb[2]) > 0.1f ? 1.0f : 0.0f;  // collision (penalised_contact_indices = base)
-    {  // default_joint_pos
+    if constexpr (rew_in(TERMS, T1_REW_COLLISION)) r[T1_REW_COLLISION] = norm3(cfb[0], cfb[1], cfb[2]) > 0.1f ? 1.0f : 0.0f;  // collision (penalised_contact_indices = base)
+    if constexpr (rew_in(TERMS, T1_REW_DEFAULT_JOINT_POS)) {  // default_joint_pos
       float jd[12], s = 0.0f;
 #pragma unroll
       for (int j = 0; j < 12; ++j) { jd[j] = dof[2 * j] - M.default_dof_pos[j]; s += jd[j] * jd[j]; }
@@ -373,7 +402,7 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
       yr = clampf(yr - 0.1f, 0.0f, 50.0f);
       r[T1_REW_DEFAULT_JOINT_POS] = expf(-yr * 100.0f) - 0.01f * sqrtf(s);
     }
-    {  // dof_acc, dof_vel
+    if constexpr (rew_in(TERMS, T1_REW_DOF_ACC)) {  // dof_acc, dof_vel
       float s5 = 0.0f, s6 = 0.0f;
 #pragma unroll
       for (int j = 0; j < 12; ++j) {
@@ -388,7 +417,7 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
     // after the clip below): with a zero scale nothing is evaluated (soft_dof_vel_limit is then not set) and the
     // term's r is +0, so it adds +0.0f to rew and its episode sum stays 0
     r[T1_REW_DOF_VEL_LIMITS] = 0.0f;
-    if (C.reward_scales[T1_REW_DOF_VEL_LIMITS] != 0.0f) {  // dof_vel_limits (t1:942-946)
+    if (rew_in(TERMS, T1_REW_DOF_VEL_LIMITS) && C.reward_scales[T1_REW_DOF_VEL_LIMITS] != 0.0f) {  // dof_vel_limits (t1:942-946)
       float s = 0.0f;
 #pragma unroll
       for (int j = 0; j < 12; ++j) {
@@ -402,7 +431,7 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
     // (a term with a zero scale has no reward function in the reference, legged_robot.py:351-384, so the state its
     // function keeps is not advanced either: feet_air_time / last_contacts here, feet_height / last_feet_z below)
     r[T1_REW_FEET_AIR_TIME] = 0.0f;
-    if (C.reward_scales[T1_REW_FEET_AIR_TIME] != 0.0f) {  // feet_air_time (mutates feet_air_time, last_contacts)
+    if (rew_in(TERMS, T1_REW_FEET_AIR_TIME) && C.reward_scales[T1_REW_FEET_AIR_TIME] != 0.0f) {  // feet_air_time (mutates feet_air_time, last_contacts)
       float sm0 = ph.stance[0], sm1 = ph.stance[1];
       if (norm3(cmd[0], cmd[1], cmd[2]) < 0.05f) { sm0 = 1.0f; sm1 = 1.0f; }
       const bool filt0 = contact0 || sm0 > 0.0f || lc[0];
@@ -417,7 +446,7 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
       r[T1_REW_FEET_AIR_TIME] = air0 + air1;
     }
     r[T1_REW_FEET_CLEARANCE] = 0.0f;
-    if (C.reward_scales[T1_REW_FEET_CLEARANCE] != 0.0f) {  // feet_clearance (mutates feet_height, last_feet_z)
+    if (rew_in(TERMS, T1_REW_FEET_CLEARANCE) && C.reward_scales[T1_REW_FEET_CLEARANCE] != 0.0f) {  // feet_clearance (mutates feet_height, last_feet_z)
       const float z0 = f0[2], z1 = f1[2];
       const float h0 = fh[0] + (z0 - lfz[0]), h1 = fh[1] + (z1 - lfz[1]);
       lfz[0] = z0; lfz[1] = z1;
@@ -429,16 +458,16 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
       fh[1] = h1 * (contact1 ? 0.0f : 1.0f);
     }
     // feet_contact_forces
-    r[T1_REW_FEET_CONTACT_FORCES] = clampf(norm3(c0[0], c0[1], c0[2]) - C.max_contact_force, 0.0f, 400.0f) +
+    if constexpr (rew_in(TERMS, T1_REW_FEET_CONTACT_FORCES)) r[T1_REW_FEET_CONTACT_FORCES] = clampf(norm3(c0[0], c0[1], c0[2]) - C.max_contact_force, 0.0f, 400.0f) +
            clampf(norm3(c1[0], c1[1], c1[2]) - C.max_contact_force, 0.0f, 400.0f);
-    {  // feet_contact_number
+    if constexpr (rew_in(TERMS, T1_REW_FEET_CONTACT_NUMBER)) {  // feet_contact_number
       float sm0 = ph.stance[0], sm1 = ph.stance[1];
       if (stand) { sm0 = 1.0f; sm1 = 1.0f; }
       const float q0 = ((contact0 ? 1.0f : 0.0f) == sm0) ? 1.0f : -0.3f;
       const float q1 = ((contact1 ? 1.0f : 0.0f) == sm1) ? 1.0f : -0.3f;
       r[T1_REW_FEET_CONTACT_NUMBER] = (q0 + q1) / 2.0f;
     }
-    {  // feet_distance, knee_distance
+    if constexpr (rew_in(TERMS, T1_REW_FEET_DISTANCE)) {  // feet_distance, knee_distance
       const float fd = norm2(f0[0] - f1[0], f0[1] - f1[1]);
       const float kd = norm2(k0[0] - k1[0], k0[1] - k1[1]);
       const float fmn = clampf(fd - C.foot_min_dist, -0.5f, 0.0f), fmx = clampf(fd - C.foot_max_dist, 0.0f, 0.5f);
@@ -446,21 +475,21 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
       r[T1_REW_FEET_DISTANCE] = (expf(-fabsf(fmn) * 100.0f) + expf(-fabsf(fmx) * 100.0f)) / 2.0f;
       r[T1_REW_KNEE_DISTANCE] = (expf(-fabsf(kmn) * 100.0f) + expf(-fabsf(kmx) * 100.0f)) / 2.0f;
     }
-    {  // feet_rotation
+    if constexpr (rew_in(TERMS, T1_REW_FEET_ROTATION)) {  // feet_rotation
       const float rot = fe[1] * fe[1] + fe[4] * fe[4];
       const float x = rot / 1.0f;
       r[T1_REW_FEET_ROTATION] = 1.0f * expf(-(x * x));
     }
     r[T1_REW_FEET_STUMBLE] = 0.0f;
-    if (C.reward_scales[T1_REW_FEET_STUMBLE] != 0.0f) {  // feet_stumble (t1:937-940): a foot pushed sideways
+    if (rew_in(TERMS, T1_REW_FEET_STUMBLE) && C.reward_scales[T1_REW_FEET_STUMBLE] != 0.0f) {  // feet_stumble (t1:937-940): a foot pushed sideways
       const bool st0 = norm2(c0[0], c0[1]) > 5.0f * fabsf(c0[2]), st1 = norm2(c1[0], c1[1]) > 5.0f * fabsf(c1[2]);
       r[T1_REW_FEET_STUMBLE] = (st0 || st1) ? 1.0f : 0.0f;
     }
-    {  // foot_slip (rigid_state[..., 10:12] as in the reference)
+    if constexpr (rew_in(TERMS, T1_REW_FOOT_SLIP)) {  // foot_slip (rigid_state[..., 10:12] as in the reference)
       const float s0 = sqrtf(norm2(f0[10], f0[11])), s1 = sqrtf(norm2(f1[10], f1[11]));
       r[T1_REW_FOOT_SLIP] = s0 * (contact0 ? 1.0f : 0.0f) + s1 * (contact1 ? 1.0f : 0.0f);
     }
-    {  // joint_pos (ref_dof_pos from the previous compute_observations)
+    if constexpr (rew_in(TERMS, T1_REW_JOINT_POS)) {  // joint_pos (ref_dof_pos from the previous compute_observations)
       float s = 0.0f;
 #pragma unroll
       for (int j = 0; j < 12; ++j) {
@@ -471,7 +500,7 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
       const float nr = sqrtf(s);
       r[T1_REW_JOINT_POS] = stand ? 1.0f : expf(-2.0f * nr) - 0.2f * clampf(nr, 0.0f, 0.5f);
     }
-    {  // low_speed
+    if constexpr (rew_in(TERMS, T1_REW_LOW_SPEED)) {  // low_speed
       const float sp = fabsf(blv[0]), cm = fabsf(cmd[0]);
       const bool low = sp < 0.5f * cm, high = sp > 1.2f * cm, ok = !(low || high);
       const bool mis = signf(blv[0]) != signf(cmd[0]);
@@ -482,12 +511,12 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
       if (mis) v = -2.0f;
       r[T1_REW_LOW_SPEED] = v * (fabsf(cmd[0]) > 0.05f ? 1.0f : 0.0f);
     }
-    {  // orientation
+    if constexpr (rew_in(TERMS, T1_REW_ORIENTATION)) {  // orientation
       const float qm = expf(-(fabsf(be[0]) + fabsf(be[1])) * 10.0f);
       const float o = expf(-norm2(pg[0], pg[1]) * 20.0f);
       r[T1_REW_ORIENTATION] = (qm + o) / 2.0f;
     }
-    {  // stand_still
+    if constexpr (rew_in(TERMS, T1_REW_STAND_STILL)) {  // stand_still
       const int idx[8] = {0, 1, 2, 3, 5, 6, 7, 8};
       const float w[10] = {2.0f, 2.0f, 1.0f, 1.0f, 1.0f, 2.0f, 2.0f, 1.0f, 1.0f, 1.0f};
       float s = 0.0f;
@@ -502,40 +531,60 @@ __device__ __forceinline__ bool post_a_core(const DynModel& M, const t1env_confi
       r[T1_REW_STAND_STILL] = stand ? expf(-s) : 0.0f;
     }
     r[T1_REW_STAND_SYSMETRY] = 0.0f;
-    if (C.reward_scales[T1_REW_STAND_SYSMETRY] != 0.0f) {  // stand_sysmetry (t1:917-925): left vs right leg, standing
+    if (rew_in(TERMS, T1_REW_STAND_SYSMETRY) && C.reward_scales[T1_REW_STAND_SYSMETRY] != 0.0f) {  // stand_sysmetry (t1:917-925): left vs right leg, standing
       float s = 0.0f;
 #pragma unroll
       for (int k = 0; k < 4; ++k) { const float d = dof[2 * k] - dof[2 * (5 + k)]; s += d * d; }
       r[T1_REW_STAND_SYSMETRY] = stand ? expf(-s) : 0.0f;
     }
     r[T1_REW_TERMINATION] = 0.0f;  // not in the clipped sum: added after the clip below
-    {  // torques
+    if constexpr (rew_in(TERMS, T1_REW_TORQUES)) {  // torques
       float s = 0.0f;
 #pragma unroll
       for (int j = 0; j < 12; ++j) s += tq[j] * tq[j];
       r[T1_REW_TORQUES] = s;
     }
-    {  // track_vel_hard
+    if constexpr (rew_in(TERMS, T1_REW_TRACK_VEL_HARD)) {  // track_vel_hard
       const float le = norm2(cmd[0] - blv[0], cmd[1] - blv[1]);
       const float ae = fabsf(cmd[2] - bav[2]);
       r[T1_REW_TRACK_VEL_HARD] = (expf(-le * 10.0f) + expf(-ae * 10.0f)) / 2.0f - 0.2f * (le + ae);
     }
-    {  // tracking_ang_vel
+    if constexpr (rew_in(TERMS, T1_REW_TRACKING_ANG_VEL)) {  // tracking_ang_vel
       const float d = cmd[2] - bav[2];
       r[T1_REW_TRACKING_ANG_VEL] = stand ? expf(-fabsf(d) * (C.tracking_sigma * 2.0f)) : expf(-(d * d) * C.tracking_sigma);
     }
-    {  // tracking_lin_vel
+    if constexpr (rew_in(TERMS, T1_REW_TRACKING_LIN_VEL)) {  // tracking_lin_vel
       const float dx = cmd[0] - blv[0], dy = cmd[1] - blv[1];
       r[T1_REW_TRACKING_LIN_VEL] = stand ? expf(-(fabsf(dx) + fabsf(dy)) * (C.tracking_sigma * 2.0f))
                     : expf(-(dx * dx + dy * dy) * C.tracking_sigma);
     }
-    {  // vel_mismatch_exp
+    if constexpr (rew_in(TERMS, T1_REW_VEL_MISMATCH_EXP)) {  // vel_mismatch_exp
       const float lm = expf(-(blv[2] * blv[2]) * 10.0f);
       const float am = expf(-norm2(bav[0], bav[1]) * 5.0f);
       r[T1_REW_VEL_MISMATCH_EXP] = (lm + am) / 2.0f;
     }
   }
   T1_PROF_MARK(18);
+  if constexpr (PART == POST_A_REW_HELPER) {  // hand this wave's terms over and leave
+    if (D.owner)
+#pragma unroll
+      for (int k = 0; k < T1_NREW; ++k)
+        if (rew_in(TERMS, k)) D.rows[k * D.stride + D.col] = r[k];
+    // One lane releases for the whole wave, as at E2: the release puts an s_waitcnt, which is wave-wide, ahead of the
+    // LDS atomic, and a wave's LDS operations complete in order, so every lane's rows are written before the count
+    // moves.  That is this hardware's behaviour, not the per-thread memory model's.
+    if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(D.count, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    T1_CLOCK_STAMP(10 + (int)(threadIdx.x >> 6));  // [14] - [17]: W4 - W7
+    return do_reset;
+  }
+  if constexpr (PART == POST_A_REWARDS && TERMS != REW_ALL) {  // the other waves' terms
+    T1_CLOCK_STAMP(6);
+    while (__hip_atomic_load(D.count, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != D.helpers) __builtin_amdgcn_s_sleep(1);
+    T1_CLOCK_STAMP(7);
+#pragma unroll
+    for (int k = 0; k < T1_NREW; ++k)
+      if (!rew_in(TERMS, k) && k != T1_REW_TERMINATION) r[k] = D.rows[k * D.stride + D.col];
+  }
   float rew = 0.0f, contrib[T1_NREW];
   if constexpr (PART != POST_A_STATE) {
 #pragma unroll

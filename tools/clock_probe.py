@@ -13,7 +13,9 @@ are per process: run it in several fresh processes.
 `tail_by_resets` splits the time of W0 (the rewards wave, which carries the finaliser) and W1 (the state wave, which
 carries reset_idx) past the epilogue barrier at the build's tail stamps -- W0: post_a_core, its reset-row work, its
 store drain, the wait at E2, the finaliser; W1: post_a_core, its reset work ahead of E2, the level sum, the wait at E2,
-what it runs behind E2 -- by the workgroup's reset count that step, over --samples further launches.
+what it runs behind E2 -- by the workgroup's reset count that step, over --samples further launches.  With the reward
+terms dealt over W4-W7: W0's own terms (stamp 0 to 6), its wait at the hand-over word (6 to 7), and the arrival there of
+each helper W4-W7 (14-17), from W0's stamp past the epilogue barrier.
 """
 import argparse
 import ctypes
@@ -32,11 +34,15 @@ from ti5_isaacgym_amd import make_t1_env  # noqa: E402
 NSUM = 10  # T1_WGSUM6_N: W0 life, S1 waits of substeps 1+, S2 waits, first S1 wait, six shift roles' S2 -> S1 tails
 
 
-# the tail stamps of a workgroup (T1_TAIL6_N = 16 ticks of 100 MHz, t1env_dyn6.hip): W0 at 0-5, W1 at 8-13
+# the tail stamps of a workgroup (T1_TAIL6_N ticks of 100 MHz, t1env_dyn6.hip): W0 at 0-7, W1 at 8-13, W4-W7 at 14-17
 TAIL_SEGMENTS = {"w0_post_a_core": (0, 1), "w0_reset_rows": (1, 2), "w0_store_drain": (2, 3), "w0_e2_wait": (3, 4),
                  "w0_finaliser": (4, 5), "w1_post_a_core": (8, 9), "w1_reset_before_e2": (9, 10),
                  "w1_level_sum_and_drain": (10, 11), "w1_e2_wait": (11, 12), "w1_after_e2": (12, 13),
-                 "w0_barrier_to_end": (0, 5), "w1_barrier_to_e2": (8, 11)}
+                 "w0_barrier_to_end": (0, 5), "w1_barrier_to_e2": (8, 11), "w1_barrier_to_end": (8, 13),
+                 "w0_own_terms": (0, 6), "w0_deal_wait": (6, 7), "w4_barrier_to_handover": (0, 14),
+                 "w5_barrier_to_handover": (0, 15), "w6_barrier_to_handover": (0, 16),
+                 "w7_barrier_to_handover": (0, 17)}
+TAIL_N = 20  # T1_TAIL6_N
 
 
 def tail_by_resets(lib, env, acts, wg, samples):
@@ -45,7 +51,7 @@ def tail_by_resets(lib, env, acts, wg, samples):
     loop-end-to-last-instruction time likewise; and how many of each launch's six last-finishing workgroups hold a reset."""
     seg = {k: {"0": [], "1": [], ">=2": []} for k in list(TAIL_SEGMENTS) + ["epilogue"]}
     last6, wgs = [], []
-    tl, tail = np.zeros((wg, 4), np.uint64), np.zeros((wg, 16), np.uint64)
+    tl, tail = np.zeros((wg, 4), np.uint64), np.zeros((wg, TAIL_N), np.uint64)
     for i in range(samples):
         env.step(acts[i % 8])
         torch.cuda.synchronize()
