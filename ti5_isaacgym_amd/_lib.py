@@ -1,4 +1,4 @@
-"""ctypes binding of libt1env_hip.so (include/t1env.h).
+"""ctypes binding of libt1env_hip.so (include/t1env.h, t1policy.h, t1render.h).
 
 The product path has no fallback: if the HIP library is missing or fails to load, importing the env
 raises.  Build it with ``python -m ti5_isaacgym_amd.build`` (or ``__graft_entry__.build()``).
@@ -112,6 +112,23 @@ POLICY_EXPORTS = ["t1policy_conv1d_forward", "t1policy_history_rows", "t1policy_
                   "t1policy_actor_forward", "t1policy_actor_forward_h", "t1policy_critic_forward",
                   "t1policy_critic_forward_h"]
 
+# include/t1render.h: the headless camera, in the same library
+RENDER_EXPORTS = ["t1render_frame"]
+RENDER_MAXCAM, RENDER_MAXPRIM = 16, 32
+
+
+class RenderCamera(C.Structure):
+    _fields_ = [("env", i32), ("follow", i32), ("eye", f32 * 3), ("target", f32 * 3), ("up", f32 * 3), ("vfov", f32)]
+
+
+class RenderPrim(C.Structure):
+    _fields_ = [("body", i32), ("kind", i32), ("a", f32 * 3), ("b", f32 * 3), ("r", f32), ("rgb", u32)]
+
+
+class RenderStyle(C.Structure):
+    _fields_ = [("light", f32 * 3), ("ambient", f32), ("terrain_rgb", (f32 * 3) * 2), ("sky_rgb", (f32 * 3) * 2)]
+
+
 _lib = None
 
 
@@ -177,6 +194,8 @@ def load():
         "t1policy_gemm_f32": ([vp, i32, vp, i32, i32, vp, vp, vp, i32, i32, i32, i32, vp], C.c_int),
         "t1policy_fold_rows": ([vp, vp, i32, i32, i32, i32, i32, i32, vp], C.c_int),
         "t1policy_gather_rows": ([vp, vp, vp, i32, vp, i32, vp], C.c_int),
+        "t1render_frame": ([vp, P(RenderCamera), i32, P(RenderPrim), i32, P(RenderStyle), i32, i32, vp, vp, vp, vp],
+                           C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

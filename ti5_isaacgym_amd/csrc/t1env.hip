@@ -71,12 +71,20 @@ struct t1env {
   unsigned* d_done;       // k_post_b block-completion counter (its last block finalises the extras)
   float* d_ep_part;       // the step kernel's per-workgroup partial extras sums (FusedArgs::ep_part)
   int16_t* d_hmax;        // coarse terrain height bound (Terrain::hmax), built by t1env_set_terrain
+  int hf_top;             // highest sample of the height field (raw units; the renderer's rays stop above it)
   float max_contact_radius;
   SubLog log;             // t1env_set_substep_log (tests): fused steps write it
   int log_on;
   hipStream_t side;       // the side-launch history shift (k_shift4c / k_shift5), forked from / joined to the step's stream
   hipEvent_t ev_fork, ev_join;
 };
+
+// what the renderer's unit (t1render.hip) may see of a handle, and the library's one error string
+int t1_fail(int code, const char* msg) { return fail(code, msg); }
+int t1_render_view(const t1env* e, RenderView* v) {
+  *v = RenderView{e->buf.rigid_state, e->terrain, e->cfg.num_envs, (float)e->hf_top * e->terrain.vscale};
+  return 0;
+}
 
 // k_physics_injected: the same decimation loop with the physics states supplied by the caller (golden
 // parity harness: the reference ran on identical injected states), so PD / lag / sensor capture are checked
@@ -709,6 +717,14 @@ int t1env_set_terrain(t1env* e, const int16_t* h, int32_t rows, int32_t cols, fl
     e->terrain.hm_rows = hr;
     e->terrain.hm_cols = hc;
     e->terrain.hm_inv_cell = 1.0f / (HMAX_CELL * hs);
+    // every sample lies in its own coarse cell's window: the highest coarse bound is the field's highest sample
+    int16_t* top = (int16_t*)malloc(sizeof(int16_t) * (size_t)hr * hc);
+    if (!top) return fail(T1ENV_E_STATE, "t1env_set_terrain: out of host memory");
+    const hipError_t err = hipMemcpy(top, e->d_hmax, sizeof(int16_t) * (size_t)hr * hc, hipMemcpyDeviceToHost);
+    e->hf_top = -32768;
+    for (size_t k = 0; err == hipSuccess && k < (size_t)hr * hc; ++k) e->hf_top = top[k] > e->hf_top ? top[k] : e->hf_top;
+    free(top);
+    HIP_TRY(err);
   }
   return 0;
 }

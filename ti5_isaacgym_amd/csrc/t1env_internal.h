@@ -53,6 +53,16 @@ int t1_launch_dyn5(const t1::DynModel* d_model, const t1env_config* d_cfg, const
 int t1_launch_dyn6(const t1::DynModel* d_model, const t1env_config* d_cfg, const t1env_buffers& B, const t1::Terrain& T,
                    const float* actions, const t1env_step_args& A, int num_envs, const t1::ShiftArgs& S,
                    const FusedArgs* fused, hipStream_t s, const SubLog* log);
+// The renderer (t1render.hip, include/t1render.h) reads a handle through this view: the body poses, the terrain and
+// the env count; t1_fail sets t1env_last_error()'s string and returns code (both in t1env.hip).
+struct RenderView {
+  const float* rigid_state;   // (N, 13, 13)
+  t1::Terrain terrain;
+  int num_envs;
+  float z_top;                // the height field's highest sample [m]
+};
+int t1_render_view(const t1env* e, RenderView* v);
+int t1_fail(int code, const char* msg);
 // The history shift as a launch of its own (t1env.hip).  beside: the step kernel it shares the CUs with -- 5: k_shift5
 // (<= 96 registers per lane, beside a k_dyn5 wave), 4: k_shift4c (<= 72, beside a k_dyn4 wave), one workgroup per CU;
 // 0: none (the paths without a step kernel), k_shift4c with four workgroups per CU.  fused: the unit handoff with the

@@ -1,8 +1,9 @@
-"""Run a trained checkpoint over the HIP env, headless (reference humanoid/scripts/play.py without its rendering,
-plotting and joystick: DESIGN.md §9).
+"""Run a trained checkpoint over the HIP env, headless (reference humanoid/scripts/play.py without its plotting and
+joystick, its camera as --render: DESIGN.md §9).
 
     python -m ti5_isaacgym_amd.scripts.play --checkpoint PATH [--num_envs 9] [--steps 2000] [--mesh_type plane]
         [--command VX VY YAW] [--state_dtype fp32|fp16] [--robot_index 0] [--out DIR]
+        [--render DIR [--render_every 2] [--render_size 640 360] [--render_follow 3.0 0.0 1.0]]
 
 The reference play's config changes (episode_length_s 1000, the noise curriculum off), its loop -- the deterministic
 policy (DHOnPolicyRunner.get_inference_policy(graphed=True): the first conv and the actor kernel as one replayed HIP
@@ -13,6 +14,11 @@ graph per observation buffer), the commands held by writing env.commands before 
                     dof_pos_target (action * action_scale), dof_pos, dof_vel, dof_torque
   DIR/summary.json  the mean per-term episode rewards over the episodes completed during the run (extras["episode"]
                     weighted by the envs that reset that step) and their count; also printed
+
+With --render DIR a camera follows --robot_index (utils/render.py: the robot's collision-level geometry, its shadow
+and the terrain; other envs' robots are not drawn).  Every --render_every-th step is rendered into one preallocated
+device buffer and written as DIR/frame_%06d.png after the loop; summary.json then also counts the "frames".  Nothing
+here encodes video: e.g. ffmpeg -framerate 50 -i DIR/frame_%06d.png -pix_fmt yuv420p play.mp4.
 
 Every logged value stays in device buffers until the run ends: no host read per step.
 """
@@ -45,7 +51,36 @@ def parse(argv=None):
     p.add_argument("--out", default="play_out")
     p.add_argument("--device", default="cuda:0")
     p.add_argument("--seed", type=int, default=123145)
-    return p.parse_args(argv)
+    p.add_argument("--render", default=None, metavar="DIR")
+    p.add_argument("--render_every", type=int, default=2, metavar="K")
+    p.add_argument("--render_size", type=int, nargs=2, default=[640, 360], metavar=("W", "H"))
+    p.add_argument("--render_follow", type=float, nargs=3, default=[3.0, 0.0, 1.0], metavar=("X", "Y", "Z"))
+    a = p.parse_args(argv)
+    check_render_args(a)
+    return a
+
+
+MAX_FRAME_BYTES = 8 << 30
+
+
+def num_frames(steps, every):
+    """the frames of a run: one after every `every`-th step"""
+    return steps // every
+
+
+def check_render_args(a):
+    """Refuse a --render run whose frame buffer (frames x width x height x 4 bytes) would exceed 8 GiB, before any
+    device work."""
+    if a.render is None:
+        return
+    w, h = a.render_size
+    if a.render_every < 1 or w < 1 or h < 1:
+        raise ValueError(f"--render_every {a.render_every} and --render_size {w} {h} must be >= 1")
+    frames = num_frames(a.steps, a.render_every)
+    if frames * w * h * 4 > MAX_FRAME_BYTES:
+        raise ValueError(f"--render: {frames} frames of {w} x {h} pixels need {frames * w * h * 4 / 2 ** 30:.1f} GiB of "
+                         "device memory, more than the 8 GiB frame buffer; raise --render_every, lower --steps or "
+                         "--render_size")
 
 
 def main(argv=None):
@@ -76,6 +111,12 @@ def main(argv=None):
     joints = torch.zeros(T, len(PER_JOINT), nj, device=dev)
     ep_keys, ep_sum = None, None
     episodes = torch.zeros((), device=dev)
+    renderer = frames = None
+    if a.render is not None:
+        from ti5_isaacgym_amd.utils.render import Camera, Renderer, write_png
+        w, h = a.render_size
+        renderer = Renderer(env, w, h, [Camera.follow(r, offset=tuple(a.render_follow))])
+        frames = torch.zeros(num_frames(T, a.render_every), 1, h, w, 4, dtype=torch.uint8, device=dev)
     obs = env.get_observations()
     with torch.inference_mode():
         for i in range(T):
@@ -88,6 +129,8 @@ def main(argv=None):
                 env.contact_forces[r, foot_l, 2], env.contact_forces[r, foot_r, 2], env.base_lin_vel[r, 0], cmd[0],
                 env.base_lin_vel[r, 1], cmd[1], env.base_lin_vel[r, 2], env.base_ang_vel[r, 2], cmd[2]))
             joints[i] = torch.stack((actions[r] * scale, env.dof_pos[r], env.dof_vel[r], env.torques[r]))
+            if renderer is not None and (i + 1) % a.render_every == 0:
+                renderer.render(frames[(i + 1) // a.render_every - 1])
             ep = infos.get("episode") or {}
             if ep_keys is None:
                 ep_keys = [k for k, v in ep.items() if isinstance(v, torch.Tensor)]
@@ -108,6 +151,15 @@ def main(argv=None):
     summary = {"checkpoint": a.checkpoint, "num_envs": a.num_envs, "steps": T, "command": list(a.command),
                "state_dtype": a.state_dtype, "episodes": count,
                "mean_episode": {k: (s / count if count else None) for k, s in zip(ep_keys or [], sums)}}
+    if renderer is not None:
+        os.makedirs(a.render, exist_ok=True)
+        images = frames.cpu().numpy()
+        for k in range(images.shape[0]):
+            write_png(os.path.join(a.render, "frame_%06d.png" % k), images[k, 0])
+        summary["frames"] = int(images.shape[0])
+        print(f"wrote {images.shape[0]} frames to {a.render}; a video: ffmpeg -framerate "
+              f"{1.0 / (float(env.dt) * a.render_every):g} -i {os.path.join(a.render, 'frame_%06d.png')} "
+              "-pix_fmt yuv420p play.mp4")
     with open(os.path.join(a.out, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     print(json.dumps(summary))

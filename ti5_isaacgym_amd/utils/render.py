@@ -1,0 +1,146 @@
+"""Headless camera over the HIP env (include/t1render.h, csrc/t1render.hip): the robot as its collision-level
+geometry, the terrain the physics stands on, one light with the robot's shadow.
+
+    from ti5_isaacgym_amd.utils.render import Camera, Renderer, write_png
+    r = Renderer(env, 640, 360, [Camera.follow(0)])
+    frame = r.render()              # (1, 360, 640, 4) uint8 on the device, one launch on the current stream
+    write_png("frame.png", frame[0].cpu().numpy())
+
+A camera sees its own env's robot and the terrain; other envs' robots are not drawn.  After a real-dynamics step
+``rigid_state`` holds the post-physics, pre-reset pose, so an env reset in that step is drawn where it fell.
+"""
+import struct
+import zlib
+
+import numpy as np
+
+from .. import _lib
+from .urdf import SELF_BODIES, load_model
+
+BOX, CAPSULE = 0, 1
+LIMB_RADIUS = 0.04            # drawing radius of the limb capsules [m] (the links' collision shapes are the boxes)
+# colours per body group, 0xBBGGRR
+COLOR_BASE, COLOR_LEFT, COLOR_RIGHT, COLOR_FEET = 0x3C3CDC, 0xD28C32, 0x50B43C, 0x32C8E6
+FEET = (6, 12)
+# light: unit direction towards the light; sky_rgb[0] at d.z = -1, [1] at d.z = +1
+STYLE = dict(light=(0.3, 0.2, 0.87 ** 0.5), ambient=0.35,
+             terrain_rgb=((0.62, 0.60, 0.55), (0.42, 0.44, 0.42)),
+             sky_rgb=((0.85, 0.90, 0.95), (0.35, 0.55, 0.90)))
+DEFAULT_VFOV = 0.9            # [rad]
+
+
+def _body_color(b):
+    return COLOR_BASE if b == 0 else COLOR_FEET if b in FEET else COLOR_LEFT if b < 7 else COLOR_RIGHT
+
+
+def robot_primitives(tab=None):
+    """The drawing table of the compiled model (utils/urdf.load_model()): a list of dicts body, kind, a, b, r, rgb.
+    The base as the bounding box of its contact points, the four self-collision boxes (shanks and feet), and for every
+    body b >= 1 with a child c a capsule from b's origin to joint_offset[c]."""
+    tab = tab or load_model()
+    prims = []
+    pts = np.array([p for p, b in zip(tab["contact_point"], tab["contact_body"]) if b == 0], dtype=np.float64)
+    lo, hi = pts.min(0), pts.max(0)
+    prims.append(dict(body=0, kind=BOX, a=tuple((lo + hi) / 2), b=tuple((hi - lo) / 2), r=0.0, rgb=COLOR_BASE))
+    for body, box in zip(SELF_BODIES, tab["self_box"]):
+        prims.append(dict(body=body, kind=BOX, a=tuple(box[:3]), b=tuple(box[3:]), r=0.0, rgb=_body_color(body)))
+    for c, b in enumerate(tab["parent"]):
+        if b >= 1:
+            prims.append(dict(body=b, kind=CAPSULE, a=(0.0, 0.0, 0.0), b=tuple(tab["joint_offset"][c]), r=LIMB_RADIUS,
+                              rgb=_body_color(b)))
+    return prims
+
+
+class Camera:
+    """A pinhole camera of env ``env``.  follow: eye and target are offsets from the env's base position, added on the
+    device (the base's yaw is not followed)."""
+
+    def __init__(self, env, eye, target, up=(0.0, 0.0, 1.0), vfov=DEFAULT_VFOV, follow=False):
+        self.env, self.follow, self.vfov = int(env), bool(follow), float(vfov)
+        self.eye, self.target, self.up = tuple(map(float, eye)), tuple(map(float, target)), tuple(map(float, up))
+
+    @classmethod
+    def fixed(cls, env, eye, target, up=(0.0, 0.0, 1.0), vfov=DEFAULT_VFOV):
+        return cls(env, eye, target, up, vfov, follow=False)
+
+    @classmethod
+    def follow(cls, env, offset=(3.0, 0.0, 1.0), look=(0.0, 0.0, -0.1), up=(0.0, 0.0, 1.0), vfov=DEFAULT_VFOV):
+        """offset and look are relative to the base link's origin, about 1 m above the soles when the robot stands: the
+        default looks slightly below it, so that the feet, their shadow and a strip of sky are in the picture."""
+        return cls(env, offset, look, up, vfov, follow=True)
+
+    def pack(self):
+        return _lib.RenderCamera(self.env, int(self.follow), (_lib.f32 * 3)(*self.eye), (_lib.f32 * 3)(*self.target),
+                                 (_lib.f32 * 3)(*self.up), self.vfov)
+
+
+def pack_prims(prims):
+    arr = (_lib.RenderPrim * max(len(prims), 1))()
+    for d, p in zip(arr, prims):
+        d.body, d.kind, d.r, d.rgb = int(p["body"]), int(p["kind"]), float(p["r"]), int(p["rgb"])
+        d.a[:], d.b[:] = [float(x) for x in p["a"]], [float(x) for x in p["b"]]
+    return arr
+
+
+def pack_style(style):
+    s = _lib.RenderStyle()
+    s.light[:] = [float(x) for x in style["light"]]
+    s.ambient = float(style["ambient"])
+    for k in range(2):
+        s.terrain_rgb[k][:] = [float(x) for x in style["terrain_rgb"][k]]
+        s.sky_rgb[k][:] = [float(x) for x in style["sky_rgb"][k]]
+    return s
+
+
+class Renderer:
+    """Preallocated device outputs for ``cameras`` at width x height over ``env`` (a T1DHStandEnv)."""
+
+    def __init__(self, env, width, height, cameras, prims=None, style=None):
+        import torch
+        self.env, self.width, self.height = env, int(width), int(height)
+        self.cameras = list(cameras)
+        n = len(self.cameras)
+        if not 1 <= n <= _lib.RENDER_MAXCAM:
+            raise ValueError(f"1 to {_lib.RENDER_MAXCAM} cameras per renderer, got {n}")
+        self.prims = list(robot_primitives() if prims is None else prims)
+        if len(self.prims) > _lib.RENDER_MAXPRIM:
+            raise ValueError(f"at most {_lib.RENDER_MAXPRIM} primitives, got {len(self.prims)}")
+        self.style = dict(STYLE if style is None else style)
+        self._cams = (_lib.RenderCamera * n)(*[c.pack() for c in self.cameras])
+        self._prims, self._style = pack_prims(self.prims), pack_style(self.style)
+        d = env.device
+        self.rgba = torch.zeros(n, self.height, self.width, 4, dtype=torch.uint8, device=d)
+        self.depth = torch.zeros(n, self.height, self.width, dtype=torch.float32, device=d)
+        self.ids = torch.zeros(n, self.height, self.width, dtype=torch.int32, device=d)
+
+    def render(self, rgba_out=None):
+        """One launch on the current stream.  Returns the (ncams, H, W, 4) uint8 device buffer it wrote: rgba_out when
+        given (same shape, contiguous), else self.rgba; self.depth and self.ids are written too."""
+        import torch
+        out = self.rgba if rgba_out is None else rgba_out
+        if rgba_out is not None and (out.shape != self.rgba.shape or out.dtype != torch.uint8 or
+                                     not out.is_contiguous() or out.device != self.rgba.device):
+            raise ValueError(f"rgba_out must be a contiguous uint8 {tuple(self.rgba.shape)} tensor on {self.rgba.device}")
+        env = self.env
+        _lib.check(env._lib.t1render_frame(env._handle, self._cams, len(self.cameras), self._prims, len(self.prims),
+                                           _lib.C.byref(self._style), self.width, self.height, out.data_ptr(),
+                                           self.depth.data_ptr(), self.ids.data_ptr(),
+                                           torch.cuda.current_stream(env.device).cuda_stream), "t1render_frame")
+        return out
+
+
+def write_png(path, hwc_uint8):
+    """An (H, W, 3) or (H, W, 4) uint8 array as an 8-bit RGB / RGBA PNG (zlib and struct only)."""
+    a = np.ascontiguousarray(hwc_uint8)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] not in (3, 4) or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("write_png takes an (H, W, 3) or (H, W, 4) uint8 array")
+    h, w, c = a.shape
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+    rows = np.zeros((h, 1 + w * c), np.uint8)   # filter type 0 in front of every row
+    rows[:, 1:] = a.reshape(h, w * c)
+    png = (b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2 if c == 3 else 6, 0, 0, 0)) +
+           chunk(b"IDAT", zlib.compress(rows.tobytes(), 6)) + chunk(b"IEND", b""))
+    with open(path, "wb") as f:
+        f.write(png)
