@@ -1,7 +1,8 @@
 /* t1render.h -- headless camera over a t1env handle: one launch ray-casts up to T1RENDER_MAXCAM pinhole cameras.
  *
  * Scene of a camera: its own env's robot (the primitives below, posed by rigid_state[env]) and the terrain the env
- * handle holds (t1env_set_terrain; the plane z = 0 without one).  Other envs' robots are NOT drawn.  The height field is
+ * handle holds (t1env_set_terrain; the plane z = 0 without one).  t1render_frame draws no other env's robot;
+ * t1render_scene (below) draws every env's and lets the height field cast shadows.  The height field is
  * the surface the physics stands on (two triangles per cell, split along (i,j)-(i+1,j+1)), restricted to the field's
  * footprint: outside it there is no terrain and a ray shows the sky.
  *
@@ -50,6 +51,39 @@ typedef struct t1render_style  { float light[3], ambient, terrain_rgb[2][3], sky
 int t1render_frame(t1env* env, const t1render_camera* cams, int32_t ncams, const t1render_prim* prims, int32_t nprims,
                    const t1render_style* style, int32_t width, int32_t height,
                    uint32_t* rgba, float* depth, int32_t* ids, void* stream);
+
+/* t1render_scene: the same camera over a larger scene, chosen by flags. */
+#define T1RENDER_SCENE_OTHERS          1  /* every env's robot is in the scene, not only the camera's */
+#define T1RENDER_SCENE_TERRAIN_SHADOW  2  /* the height field casts shadows (no effect on the plane) */
+#define T1RENDER_SCENE_BRUTE           4  /* test hook: no culling, every env's primitives for every ray */
+
+/* With OTHERS the primitive set is prims posed by rigid_state[n] for every n in [0, num_envs); ray, hit range, the
+ * entry-only rule, shading and colour are those above.  The nearest entry wins; at exactly equal t the lower env, then
+ * the lower primitive index; the terrain still wins a tie against a primitive.  The shadow ray tests the same primitive
+ * set as the camera ray, so a neighbour shadows the camera's robot and the ground under it.  With TERRAIN_SHADOW the
+ * shadow ray (origin hit + 1e-3 n, direction L) is also cast against the height field by the camera ray's rule: a hit
+ * at t in (0.05, 200] darkens the pixel; the plane casts nothing.  envs (int32, the shape of ids, may be NULL): the env
+ * whose robot the pixel shows, -1 for terrain and sky.  With flags == 0 rgba, depth and ids are bit for bit what
+ * t1render_frame writes, and envs is the camera's env where ids > 0.
+ *
+ * Culling: with OTHERS a pre-pass over the envs writes a padded bounding sphere of each posed robot (from rigid_state,
+ * whatever the poses are; quaternions are taken to be unit ones) and one bit per env and camera into the workspace, and
+ * the render kernel tests only the robots that can touch a tile's rays or cast a shadow into it.  Culling is invisible:
+ * with and without BRUTE the four planes are equal to the bit.  BRUTE needs no workspace and costs num_envs per pixel.
+ *
+ * workspace: device memory of at least t1render_scene_workspace_bytes(num_envs, ncams) bytes on a 16-byte boundary,
+ * needed with OTHERS and without BRUTE (else it may be NULL); its content before the call does not matter and the call
+ * writes nowhere else but the outputs.  A memset and up to three launches in stream order on `stream`; no allocation,
+ * no synchronisation, no host read.  t1render_scene_workspace_bytes returns -1 for num_envs < 0 or ncams outside
+ * [1, T1RENDER_MAXCAM] and never shrinks as either grows.
+ * Errors, all before any device work: everything t1render_frame refuses; T1ENV_E_ARG also for an unknown flag bit,
+ * OTHERS without BRUTE and with a NULL workspace, and a non-NULL workspace that is smaller than the query's size or
+ * off a 16-byte boundary. */
+long long t1render_scene_workspace_bytes(int32_t num_envs, int32_t ncams);
+int t1render_scene(t1env* env, const t1render_camera* cams, int32_t ncams, const t1render_prim* prims, int32_t nprims,
+                   const t1render_style* style, int32_t flags, int32_t width, int32_t height,
+                   uint32_t* rgba, float* depth, int32_t* ids, int32_t* envs,
+                   void* workspace, long long workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

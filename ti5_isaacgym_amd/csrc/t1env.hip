@@ -72,6 +72,7 @@ struct t1env {
   float* d_ep_part;       // the step kernel's per-workgroup partial extras sums (FusedArgs::ep_part)
   int16_t* d_hmax;        // coarse terrain height bound (Terrain::hmax), built by t1env_set_terrain
   int hf_top;             // highest sample of the height field (raw units; the renderer's rays stop above it)
+  int hf_bot;             // lowest sample (raw units; the renderer's shadow culling stops below it)
   float max_contact_radius;
   SubLog log;             // t1env_set_substep_log (tests): fused steps write it
   int log_on;
@@ -82,7 +83,8 @@ struct t1env {
 // what the renderer's unit (t1render.hip) may see of a handle, and the library's one error string
 int t1_fail(int code, const char* msg) { return fail(code, msg); }
 int t1_render_view(const t1env* e, RenderView* v) {
-  *v = RenderView{e->buf.rigid_state, e->terrain, e->cfg.num_envs, (float)e->hf_top * e->terrain.vscale};
+  *v = RenderView{e->buf.rigid_state, e->terrain, e->cfg.num_envs, (float)e->hf_top * e->terrain.vscale,
+                   e->terrain.type != 0 ? (float)e->hf_bot * e->terrain.vscale : 0.0f};
   return 0;
 }
 
@@ -725,6 +727,14 @@ int t1env_set_terrain(t1env* e, const int16_t* h, int32_t rows, int32_t cols, fl
     for (size_t k = 0; err == hipSuccess && k < (size_t)hr * hc; ++k) e->hf_top = top[k] > e->hf_top ? top[k] : e->hf_top;
     free(top);
     HIP_TRY(err);
+    // the lowest sample, from a host copy of the field (set-up time only)
+    int16_t* all = (int16_t*)malloc(sizeof(int16_t) * (size_t)rows * cols);
+    if (!all) return fail(T1ENV_E_STATE, "t1env_set_terrain: out of host memory");
+    const hipError_t err2 = hipMemcpy(all, h, sizeof(int16_t) * (size_t)rows * cols, hipMemcpyDeviceToHost);
+    e->hf_bot = 32767;
+    for (size_t k = 0; err2 == hipSuccess && k < (size_t)rows * cols; ++k) e->hf_bot = all[k] < e->hf_bot ? all[k] : e->hf_bot;
+    free(all);
+    HIP_TRY(err2);
   }
   return 0;
 }

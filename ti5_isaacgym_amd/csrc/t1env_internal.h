@@ -60,6 +60,7 @@ struct RenderView {
   t1::Terrain terrain;
   int num_envs;
   float z_top;                // the height field's highest sample [m]
+  float z_bot;                // its lowest sample [m] (0 on the plane): no terrain receives a shadow below it
 };
 int t1_render_view(const t1env* e, RenderView* v);
 int t1_fail(int code, const char* msg);

@@ -3,7 +3,8 @@ joystick, its camera as --render: DESIGN.md §9).
 
     python -m ti5_isaacgym_amd.scripts.play --checkpoint PATH [--num_envs 9] [--steps 2000] [--mesh_type plane]
         [--command VX VY YAW] [--state_dtype fp32|fp16] [--robot_index 0] [--out DIR]
-        [--render DIR [--render_every 2] [--render_size 640 360] [--render_follow 3.0 0.0 1.0]]
+        [--render DIR [--render_every 2] [--render_size 640 360] [--render_follow 3.0 0.0 1.0]
+                      [--render_scene own|all] [--render_terrain_shadow]]
 
 The reference play's config changes (episode_length_s 1000, the noise curriculum off), its loop -- the deterministic
 policy (DHOnPolicyRunner.get_inference_policy(graphed=True): the first conv and the actor kernel as one replayed HIP
@@ -16,7 +17,8 @@ graph per observation buffer), the commands held by writing env.commands before 
                     weighted by the envs that reset that step) and their count; also printed
 
 With --render DIR a camera follows --robot_index (utils/render.py: the robot's collision-level geometry, its shadow
-and the terrain; other envs' robots are not drawn).  Every --render_every-th step is rendered into one preallocated
+and the terrain).  --render_scene all draws every env's robot and its shadow, as the reference's camera films all of
+them (own, the default: only the followed one); --render_terrain_shadow lets a height field cast shadows too.  Every --render_every-th step is rendered into one preallocated
 device buffer and written as DIR/frame_%06d.png after the loop; summary.json then also counts the "frames".  Nothing
 here encodes video: e.g. ffmpeg -framerate 50 -i DIR/frame_%06d.png -pix_fmt yuv420p play.mp4.
 
@@ -55,6 +57,8 @@ def parse(argv=None):
     p.add_argument("--render_every", type=int, default=2, metavar="K")
     p.add_argument("--render_size", type=int, nargs=2, default=[640, 360], metavar=("W", "H"))
     p.add_argument("--render_follow", type=float, nargs=3, default=[3.0, 0.0, 1.0], metavar=("X", "Y", "Z"))
+    p.add_argument("--render_scene", choices=["own", "all"], default="own")
+    p.add_argument("--render_terrain_shadow", action="store_true")
     a = p.parse_args(argv)
     check_render_args(a)
     return a
@@ -115,7 +119,8 @@ def main(argv=None):
     if a.render is not None:
         from ti5_isaacgym_amd.utils.render import Camera, Renderer, write_png
         w, h = a.render_size
-        renderer = Renderer(env, w, h, [Camera.follow(r, offset=tuple(a.render_follow))])
+        renderer = Renderer(env, w, h, [Camera.follow(r, offset=tuple(a.render_follow))],
+                            others=a.render_scene == "all", terrain_shadow=a.render_terrain_shadow)
         frames = torch.zeros(num_frames(T, a.render_every), 1, h, w, 4, dtype=torch.uint8, device=dev)
     obs = env.get_observations()
     with torch.inference_mode():

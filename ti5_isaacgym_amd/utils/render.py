@@ -6,8 +6,11 @@ geometry, the terrain the physics stands on, one light with the robot's shadow.
     frame = r.render()              # (1, 360, 640, 4) uint8 on the device, one launch on the current stream
     write_png("frame.png", frame[0].cpu().numpy())
 
-A camera sees its own env's robot and the terrain; other envs' robots are not drawn.  After a real-dynamics step
-``rigid_state`` holds the post-physics, pre-reset pose, so an env reset in that step is drawn where it fell.
+By default a camera sees its own env's robot and the terrain.  ``Renderer(..., others=True)`` puts every env's robot
+into the scene (t1render_scene: culled on the device, so a frame does not cost num_envs per pixel; ``self.envs`` then
+tells whose robot a pixel shows), ``terrain_shadow=True`` lets the height field cast shadows as well.  After a
+real-dynamics step ``rigid_state`` holds the post-physics, pre-reset pose, so an env reset in that step is drawn where
+it fell.
 """
 import struct
 import zlib
@@ -93,9 +96,11 @@ def pack_style(style):
 
 
 class Renderer:
-    """Preallocated device outputs for ``cameras`` at width x height over ``env`` (a T1DHStandEnv)."""
+    """Preallocated device outputs for ``cameras`` at width x height over ``env`` (a T1DHStandEnv).  others: every
+    env's robot is drawn and casts shadows, not only the camera's own; terrain_shadow: the height field casts shadows.
+    With both off render() is t1render_frame; else t1render_scene, with the workspace allocated here, once."""
 
-    def __init__(self, env, width, height, cameras, prims=None, style=None):
+    def __init__(self, env, width, height, cameras, prims=None, style=None, others=False, terrain_shadow=False):
         import torch
         self.env, self.width, self.height = env, int(width), int(height)
         self.cameras = list(cameras)
@@ -112,20 +117,40 @@ class Renderer:
         self.rgba = torch.zeros(n, self.height, self.width, 4, dtype=torch.uint8, device=d)
         self.depth = torch.zeros(n, self.height, self.width, dtype=torch.float32, device=d)
         self.ids = torch.zeros(n, self.height, self.width, dtype=torch.int32, device=d)
+        self.others, self.terrain_shadow = bool(others), bool(terrain_shadow)
+        self.flags = (_lib.RENDER_SCENE_OTHERS if self.others else 0) | \
+            (_lib.RENDER_SCENE_TERRAIN_SHADOW if self.terrain_shadow else 0)
+        # whose robot a pixel shows (-1: terrain, sky); stays -1 while both switches are off (t1render_frame has no such plane)
+        self.envs = torch.full((n, self.height, self.width), -1, dtype=torch.int32, device=d)
+        self.workspace = None
+        if self.others:
+            size = env._lib.t1render_scene_workspace_bytes(int(env.num_envs), n)
+            if size < 0:
+                raise ValueError(f"t1render_scene_workspace_bytes({env.num_envs}, {n}) refused")
+            self.workspace = torch.zeros(size, dtype=torch.uint8, device=d)   # torch allocates on 256-byte boundaries
 
     def render(self, rgba_out=None):
-        """One launch on the current stream.  Returns the (ncams, H, W, 4) uint8 device buffer it wrote: rgba_out when
-        given (same shape, contiguous), else self.rgba; self.depth and self.ids are written too."""
+        """On the current stream (one launch; with others a memset and three).  Returns the (ncams, H, W, 4) uint8
+        device buffer it wrote: rgba_out when given (same shape, contiguous), else self.rgba; self.depth and self.ids
+        are written too, and self.envs whenever others or terrain_shadow is on."""
         import torch
         out = self.rgba if rgba_out is None else rgba_out
         if rgba_out is not None and (out.shape != self.rgba.shape or out.dtype != torch.uint8 or
                                      not out.is_contiguous() or out.device != self.rgba.device):
             raise ValueError(f"rgba_out must be a contiguous uint8 {tuple(self.rgba.shape)} tensor on {self.rgba.device}")
         env = self.env
+        stream = torch.cuda.current_stream(env.device).cuda_stream
+        if self.flags:
+            ws = self.workspace
+            _lib.check(env._lib.t1render_scene(env._handle, self._cams, len(self.cameras), self._prims, len(self.prims),
+                                               _lib.C.byref(self._style), self.flags, self.width, self.height,
+                                               out.data_ptr(), self.depth.data_ptr(), self.ids.data_ptr(),
+                                               self.envs.data_ptr(), ws.data_ptr() if ws is not None else None,
+                                               ws.numel() if ws is not None else 0, stream), "t1render_scene")
+            return out
         _lib.check(env._lib.t1render_frame(env._handle, self._cams, len(self.cameras), self._prims, len(self.prims),
                                            _lib.C.byref(self._style), self.width, self.height, out.data_ptr(),
-                                           self.depth.data_ptr(), self.ids.data_ptr(),
-                                           torch.cuda.current_stream(env.device).cuda_stream), "t1render_frame")
+                                           self.depth.data_ptr(), self.ids.data_ptr(), stream), "t1render_frame")
         return out
 
 

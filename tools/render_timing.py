@@ -1,9 +1,14 @@
 """Time the headless camera (t1render_frame) with device events and write profiles/render_timing.json.
 
     python tools/render_timing.py [--num-envs 4096] [--out profiles/render_timing.json]
+    python tools/render_timing.py --scene [--out profiles/render_scene_timing.json]
 
 One follow camera at 640 x 360 and at 1920 x 1080, on the plane and on the default trimesh: 20 launches after 3
-warm-ups, each between two events; the env's step (random actions, the same env) timed the same way beside it."""
+warm-ups, each between two events; the env's step (random actions, the same env) timed the same way beside it.
+
+--scene times t1render_scene instead: 9 and 4096 envs on the plane, 4096 on the default trimesh, each with
+t1render_frame in the same run as the yardstick, then flags = 0, OTHERS and OTHERS | TERRAIN_SHADOW through the new
+entry; and OTHERS at 32768 envs on the plane, which shows what the pre-pass over the envs costs."""
 import argparse
 import json
 import os
@@ -30,13 +35,85 @@ def timed(fn):
     return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
 
 
+SIZES = ((640, 360), (1920, 1080))
+
+
+def scene_call(r, flags):
+    """r.render() with the flags given, through t1render_scene whatever they are (a Renderer with both switches off
+    calls t1render_frame)."""
+    from ti5_isaacgym_amd import _lib
+    env, ws = r.env, r.workspace
+
+    def call():
+        _lib.check(env._lib.t1render_scene(env._handle, r._cams, len(r.cameras), r._prims, len(r.prims),
+                                           _lib.C.byref(r._style), flags, r.width, r.height, r.rgba.data_ptr(),
+                                           r.depth.data_ptr(), r.ids.data_ptr(), r.envs.data_ptr(),
+                                           ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0,
+                                           torch.cuda.current_stream(env.device).cuda_stream), "t1render_scene")
+    return call
+
+
+def scene_rows(env, others_only=False):
+    from ti5_isaacgym_amd import _lib
+    from ti5_isaacgym_amd.utils.render import Camera, Renderer
+    O, T = _lib.RENDER_SCENE_OTHERS, _lib.RENDER_SCENE_TERRAIN_SHADOW
+    row = {}
+    for w, h in SIZES:
+        plain = Renderer(env, w, h, [Camera.follow(0)])
+        r = Renderer(env, w, h, [Camera.follow(0)], others=True, terrain_shadow=True)
+        cell = {}
+        if not others_only:
+            cell["t1render_frame"] = timed(plain.render)
+            cell["flags_0"] = timed(scene_call(r, 0))
+            cell["t1render_frame_again"] = timed(plain.render)   # the run-to-run spread of the yardstick
+        cell["others"] = timed(scene_call(r, O))
+        if not others_only:
+            cell["others_terrain_shadow"] = timed(scene_call(r, O | T))
+        seen = torch.unique(r.envs)
+        cell["envs_in_the_picture"] = int((seen >= 0).sum())
+        row[f"{w}x{h}"] = cell
+    return row
+
+
+def prepared(num_envs, mesh):
+    from ti5_isaacgym_amd import make_t1_env
+    env = make_t1_env(num_envs=num_envs, mesh_type=mesh, seed=3, device="cuda:0")
+    env.reset()
+    g = torch.Generator(device="cuda:0").manual_seed(1)
+    act = torch.randn(num_envs, 12, device="cuda:0", generator=g) * 0.3
+    for _ in range(20):
+        env.step(act)
+    return env
+
+
+def scene_main(out):
+    res = {"device": torch.cuda.get_device_name(0), "warmup": WARMUP, "launches": LAUNCHES, "cameras": 1,
+           "method": "one event pair per call, calls back to back on one stream; a call with OTHERS is a memset and "
+                     "three launches", "camera": "Camera.follow(0)"}
+    for mesh, sizes in (("plane", (9, 4096)), ("trimesh", (4096,))):
+        for n in sizes:
+            env = prepared(n, mesh)
+            res[f"{mesh}_{n}"] = scene_rows(env)
+            del env
+    env = prepared(32768, "plane")
+    res["plane_32768"] = scene_rows(env, others_only=True)
+    del env
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     from ti5_isaacgym_amd import make_t1_env
     from ti5_isaacgym_amd.utils.render import Camera, Renderer
     ap = argparse.ArgumentParser()
     ap.add_argument("--num-envs", type=int, default=4096)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "render_timing.json"))
+    ap.add_argument("--scene", action="store_true")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.scene:
+        return scene_main(a.out or os.path.join(REPO, "profiles", "render_scene_timing.json"))
+    a.out = a.out or os.path.join(REPO, "profiles", "render_timing.json")
     res = {"device": torch.cuda.get_device_name(0), "num_envs": a.num_envs, "warmup": WARMUP, "launches": LAUNCHES,
            "cameras": 1, "method": "one event pair per launch, launches back to back on one stream"}
     for mesh in ("plane", "trimesh"):
