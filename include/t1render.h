@@ -85,6 +85,60 @@ int t1render_scene(t1env* env, const t1render_camera* cams, int32_t ncams, const
                    uint32_t* rgba, float* depth, int32_t* ids, int32_t* envs,
                    void* workspace, long long workspace_bytes, void* stream);
 
+/* t1render_mesh_*: the same camera with the robot drawn as triangle meshes (its URDF's visual meshes) instead of the
+ * primitives.
+ *
+ * t1render_mesh_create: tri (ntri, 3, 3) float32 vertices in the frame of their body, body (ntri) in [0, 13), rgb
+ * (ntri) 0x00BBGGRR: host memory.  It builds one bounding volume hierarchy per body on the host (csrc/t1render_bvh.h)
+ * and uploads nodes and triangles once; it is the only call here that allocates or synchronises.  ntri == 0 is legal:
+ * a robot that is not drawn.  T1ENV_E_ARG, before any device work: a null pointer, ntri outside [0, 2^20], a body
+ * outside [0, 13), a vertex that is not finite.  t1render_mesh_destroy frees the handle (NULL: nothing to do; a handle
+ * that is not live: T1ENV_E_ARG).  t1render_mesh_info: the triangle count, the trees' node count, the depth of their
+ * deepest leaf and, per body, the padded radius about the body's origin beyond which nothing of it lies (0: no
+ * triangle); each output may be NULL.
+ *
+ * The picture of t1render_mesh_scene.  The robot of env n is the set of world triangles p_b + R_b v, v a vertex of a
+ * triangle of body b, p_b = rigid_state[n][b][0:3] and R_b the rotation of the quaternion rigid_state[n][b][3:7] =
+ * (x, y, z, w): rows (1 - 2(yy + zz), 2(xy - zw), 2(xz + yw)), (2(xy + zw), 1 - 2(xx + zz), 2(yz - xw)), (2(xz - yw),
+ * 2(yz + xw), 1 - 2(xx + yy)).  No primitive is drawn by this call.  A triangle is hit from either side; a triangle of
+ * zero area is never hit.  Two rules of the intersection decide hits at a triangle's rim.  The in-triangle test is
+ * widened by 1e-5 in the barycentric coordinates (u >= -1e-5, v >= -1e-5, u + v <= 1 + 1e-5), so that a ray along an
+ * edge two triangles share cannot slip between them.  And a hit counts only where the hit point, computed in float in
+ * the body's frame, lies inside the axis-aligned box of the triangle's three vertices widened by 1e-5 (|o'|_1 + radius),
+ * o' being the ray's origin in the body's frame and radius the body's (t1render_mesh_info): this is what lets every
+ * bound of the hierarchy err only towards visiting, and it drops a hit whose ray grazes the triangle's plane at less
+ * than about 0.3 degrees, where float no longer places the hit point.  Hits count for t in (0.05, 200] along the camera ray, the nearest wins; at exactly equal t
+ * the lower env, then the lower triangle index (the caller's); the terrain still wins a tie against the robot.  The
+ * normal is the triangle's geometric normal, turned to face the ray's origin (flat shading); the colour is the
+ * triangle's rgb.  Ambient, the lit rule, sky, checker and channel rounding are those above.  The shadow ray starts at
+ * hit + 1e-3 n and goes towards the light; any triangle at 0 < t <= 200 blocks it, with TERRAIN_SHADOW the height
+ * field too (by the rule above), and with OTHERS the triangles of every env.  Without OTHERS the scene holds the
+ * camera's env alone.
+ *
+ * flags: T1RENDER_SCENE_OTHERS, _TERRAIN_SHADOW and _BRUTE (no env culling) as above, and T1RENDER_MESH_BRUTE.  Planes:
+ * rgba and depth as above; ids 1 + body, 0 terrain, -1 sky; envs as t1render_scene's; tris (int32) the caller's
+ * index of the triangle shown, -1 for terrain and sky.  depth, ids, envs and tris may each be NULL.  All planes are
+ * equal to the bit with and without MESH_BRUTE and with and without SCENE_BRUTE.  With an ntri == 0 mesh and
+ * flags == 0, rgba, depth and ids are what t1render_frame writes with nprims == 0.
+ *
+ * Culling and workspace: t1render_scene's, with a robot's sphere taken from the meshes' radii (t1render_mesh_info),
+ * not from the primitives.  workspace: at least t1render_mesh_workspace_bytes(num_envs, ncams) bytes of device memory
+ * on a 16-byte boundary, needed with OTHERS and without SCENE_BRUTE (else it may be NULL).  A memset and at most three
+ * launches in stream order on `stream`; no allocation, no synchronisation, no host read, no write to any env buffer.
+ * Errors, all before any device work, outputs and workspace untouched: what t1render_scene refuses of env, cams,
+ * style, sizes, flags and workspace, and T1ENV_E_ARG for a mesh that is NULL or not a live handle.
+ * Still not drawn: smooth shading, textures and materials; the terrain is the height field, not a mesh. */
+typedef struct t1render_mesh t1render_mesh;   /* opaque, device-resident */
+int t1render_mesh_create(const float* tri, const int32_t* body, const uint32_t* rgb, int32_t ntri, t1render_mesh** out);
+int t1render_mesh_destroy(t1render_mesh* m);
+int t1render_mesh_info(const t1render_mesh* m, int32_t* ntri, int32_t* nnodes, int32_t* max_depth, float* radius /*[13]*/);
+#define T1RENDER_MESH_BRUTE 8   /* test hook: no BVH, every triangle of a body tested once the body's root box is entered */
+long long t1render_mesh_workspace_bytes(int32_t num_envs, int32_t ncams);
+int t1render_mesh_scene(t1env* env, const t1render_camera* cams, int32_t ncams, const t1render_mesh* mesh,
+                        const t1render_style* style, int32_t flags, int32_t width, int32_t height,
+                        uint32_t* rgba, float* depth, int32_t* ids, int32_t* envs, int32_t* tris,
+                        void* workspace, long long workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

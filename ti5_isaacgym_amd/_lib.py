@@ -115,7 +115,10 @@ POLICY_EXPORTS = ["t1policy_conv1d_forward", "t1policy_history_rows", "t1policy_
 # include/t1render.h: the headless camera, in the same library
 RENDER_EXPORTS = ["t1render_frame"]
 RENDER_SCENE_EXPORTS = ["t1render_scene_workspace_bytes", "t1render_scene"]
+RENDER_MESH_EXPORTS = ["t1render_mesh_create", "t1render_mesh_destroy", "t1render_mesh_info",
+                       "t1render_mesh_workspace_bytes", "t1render_mesh_scene"]
 RENDER_SCENE_OTHERS, RENDER_SCENE_TERRAIN_SHADOW, RENDER_SCENE_BRUTE = 1, 2, 4
+RENDER_MESH_BRUTE = 8
 RENDER_MAXCAM, RENDER_MAXPRIM = 16, 32
 
 
@@ -201,6 +204,12 @@ def load():
         "t1render_scene_workspace_bytes": ([i32, i32], C.c_longlong),
         "t1render_scene": ([vp, P(RenderCamera), i32, P(RenderPrim), i32, P(RenderStyle), i32, i32, i32, vp, vp, vp, vp,
                             vp, C.c_longlong, vp], C.c_int),
+        "t1render_mesh_create": ([P(f32), i32p, P(u32), i32, P(vp)], C.c_int),
+        "t1render_mesh_destroy": ([vp], C.c_int),
+        "t1render_mesh_info": ([vp, i32p, i32p, i32p, P(f32)], C.c_int),
+        "t1render_mesh_workspace_bytes": ([i32, i32], C.c_longlong),
+        "t1render_mesh_scene": ([vp, P(RenderCamera), i32, vp, P(RenderStyle), i32, i32, i32, vp, vp, vp, vp, vp,
+                                 vp, C.c_longlong, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

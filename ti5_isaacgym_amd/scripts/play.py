@@ -4,7 +4,7 @@ joystick, its camera as --render: DESIGN.md §9).
     python -m ti5_isaacgym_amd.scripts.play --checkpoint PATH [--num_envs 9] [--steps 2000] [--mesh_type plane]
         [--command VX VY YAW] [--state_dtype fp32|fp16] [--robot_index 0] [--out DIR]
         [--render DIR [--render_every 2] [--render_size 640 360] [--render_follow 3.0 0.0 1.0]
-                      [--render_scene own|all] [--render_terrain_shadow]]
+                      [--render_scene own|all] [--render_terrain_shadow] [--render_urdf PATH]]
 
 The reference play's config changes (episode_length_s 1000, the noise curriculum off), its loop -- the deterministic
 policy (DHOnPolicyRunner.get_inference_policy(graphed=True): the first conv and the actor kernel as one replayed HIP
@@ -18,7 +18,11 @@ graph per observation buffer), the commands held by writing env.commands before 
 
 With --render DIR a camera follows --robot_index (utils/render.py: the robot's collision-level geometry, its shadow
 and the terrain).  --render_scene all draws every env's robot and its shadow, as the reference's camera films all of
-them (own, the default: only the followed one); --render_terrain_shadow lets a height field cast shadows too.  Every --render_every-th step is rendered into one preallocated
+them (own, the default: only the followed one); --render_terrain_shadow lets a height field cast shadows too.
+--render_urdf PATH draws the visual meshes of that robot description (utils/render.RobotMesh.from_urdf; the mesh files
+it names must lie where it says) instead of the collision-level primitives; it composes with the two switches, and
+summary.json then also counts the last frame's "robot_pixels".  The repository ships no meshes: pass your copy of the
+robot description.  Every --render_every-th step is rendered into one preallocated
 device buffer and written as DIR/frame_%06d.png after the loop; summary.json then also counts the "frames".  Nothing
 here encodes video: e.g. ffmpeg -framerate 50 -i DIR/frame_%06d.png -pix_fmt yuv420p play.mp4.
 
@@ -59,6 +63,7 @@ def parse(argv=None):
     p.add_argument("--render_follow", type=float, nargs=3, default=[3.0, 0.0, 1.0], metavar=("X", "Y", "Z"))
     p.add_argument("--render_scene", choices=["own", "all"], default="own")
     p.add_argument("--render_terrain_shadow", action="store_true")
+    p.add_argument("--render_urdf", default=None, metavar="PATH")
     a = p.parse_args(argv)
     check_render_args(a)
     return a
@@ -74,7 +79,12 @@ def num_frames(steps, every):
 
 def check_render_args(a):
     """Refuse a --render run whose frame buffer (frames x width x height x 4 bytes) would exceed 8 GiB, before any
-    device work."""
+    device work; --render_urdf without --render, or naming a file that does not exist, likewise."""
+    if a.render_urdf is not None:
+        if a.render is None:
+            raise ValueError("--render_urdf needs --render DIR")
+        if not os.path.isfile(a.render_urdf):
+            raise FileNotFoundError(f"--render_urdf {a.render_urdf}: no such file")
     if a.render is None:
         return
     w, h = a.render_size
@@ -117,10 +127,11 @@ def main(argv=None):
     episodes = torch.zeros((), device=dev)
     renderer = frames = None
     if a.render is not None:
-        from ti5_isaacgym_amd.utils.render import Camera, Renderer, write_png
+        from ti5_isaacgym_amd.utils.render import Camera, Renderer, RobotMesh, write_png
         w, h = a.render_size
+        mesh = RobotMesh.from_urdf(a.render_urdf) if a.render_urdf is not None else None
         renderer = Renderer(env, w, h, [Camera.follow(r, offset=tuple(a.render_follow))],
-                            others=a.render_scene == "all", terrain_shadow=a.render_terrain_shadow)
+                            others=a.render_scene == "all", terrain_shadow=a.render_terrain_shadow, mesh=mesh)
         frames = torch.zeros(num_frames(T, a.render_every), 1, h, w, 4, dtype=torch.uint8, device=dev)
     obs = env.get_observations()
     with torch.inference_mode():
@@ -162,6 +173,9 @@ def main(argv=None):
         for k in range(images.shape[0]):
             write_png(os.path.join(a.render, "frame_%06d.png" % k), images[k, 0])
         summary["frames"] = int(images.shape[0])
+        if renderer.mesh is not None:
+            summary["robot_pixels"] = int((renderer.ids > 0).sum()) if images.shape[0] else 0
+            renderer.mesh.close()
         print(f"wrote {images.shape[0]} frames to {a.render}; a video: ffmpeg -framerate "
               f"{1.0 / (float(env.dt) * a.render_every):g} -i {os.path.join(a.render, 'frame_%06d.png')} "
               "-pix_fmt yuv420p play.mp4")

@@ -8,7 +8,10 @@ geometry, the terrain the physics stands on, one light with the robot's shadow.
 
 By default a camera sees its own env's robot and the terrain.  ``Renderer(..., others=True)`` puts every env's robot
 into the scene (t1render_scene: culled on the device, so a frame does not cost num_envs per pixel; ``self.envs`` then
-tells whose robot a pixel shows), ``terrain_shadow=True`` lets the height field cast shadows as well.  After a
+tells whose robot a pixel shows), ``terrain_shadow=True`` lets the height field cast shadows as well.
+``Renderer(..., mesh=RobotMesh.from_urdf(path))`` draws the robot as the URDF's visual meshes instead of the
+primitives (t1render_mesh_scene: a bounding volume hierarchy per body, walked on the device; ``self.tris`` tells which
+triangle a pixel shows); smooth shading, textures and materials are not drawn.  After a
 real-dynamics step ``rigid_state`` holds the post-physics, pre-reset pose, so an env reset in that step is drawn where
 it fell.
 """
@@ -95,12 +98,64 @@ def pack_style(style):
     return s
 
 
+class RobotMesh:
+    """The robot as triangle meshes on the device (t1render_mesh_create: one bounding volume hierarchy per body, built
+    on the host and uploaded once).  tri (T, 3, 3) float32 vertices in the frame of their body, body (T,) in [0, 13),
+    rgb (T,) 0xBBGGRR.  Owns the handle: close() (or the garbage collector) destroys it."""
+
+    def __init__(self, tri, body, rgb):
+        tri = np.ascontiguousarray(tri, dtype=np.float32)
+        body = np.ascontiguousarray(body, dtype=np.int32)
+        rgb = np.ascontiguousarray(rgb, dtype=np.uint32)
+        if tri.ndim != 3 or tri.shape[1:] != (3, 3) or body.shape != (len(tri),) or rgb.shape != (len(tri),):
+            raise ValueError("RobotMesh takes tri (T, 3, 3), body (T,) and rgb (T,)")
+        self._lib = _lib.load()
+        self._handle = _lib.C.c_void_p()
+        self.ntri = len(tri)
+        _lib.check(self._lib.t1render_mesh_create(tri.ctypes.data_as(_lib.C.POINTER(_lib.f32)),
+                                                  body.ctypes.data_as(_lib.C.POINTER(_lib.i32)),
+                                                  rgb.ctypes.data_as(_lib.C.POINTER(_lib.u32)), self.ntri,
+                                                  _lib.C.byref(self._handle)), "t1render_mesh_create")
+
+    @classmethod
+    def from_urdf(cls, path, missing_ok=False):
+        """The URDF's visual meshes (utils/urdf.visual_meshes), coloured by source link: the feet COLOR_FEET, the
+        left and right legs and arm links COLOR_LEFT and COLOR_RIGHT, the rest of the base group COLOR_BASE."""
+        from .urdf import visual_meshes
+        m = visual_meshes(path, missing_ok=missing_ok)
+        per_link = np.array([COLOR_LEFT if n.startswith(("L_", "leg_l")) else
+                             COLOR_RIGHT if n.startswith(("R_", "leg_r")) else COLOR_BASE for n in m["links"]] + [0],
+                            dtype=np.uint32)
+        rgb = per_link[m["link"]]
+        rgb[np.isin(m["body"], FEET)] = COLOR_FEET
+        return cls(m["tri"], m["body"], rgb)
+
+    def info(self):
+        """dict(ntri, nnodes, max_depth, radius (13,)): t1render_mesh_info."""
+        n, k, d = _lib.i32(), _lib.i32(), _lib.i32()
+        r = (_lib.f32 * 13)()
+        _lib.check(self._lib.t1render_mesh_info(self._handle, _lib.C.byref(n), _lib.C.byref(k), _lib.C.byref(d), r),
+                   "t1render_mesh_info")
+        return dict(ntri=n.value, nnodes=k.value, max_depth=d.value, radius=np.array(r[:], dtype=np.float32))
+
+    def close(self):
+        if getattr(self, "_handle", None):
+            self._lib.t1render_mesh_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        self.close()
+
+
 class Renderer:
     """Preallocated device outputs for ``cameras`` at width x height over ``env`` (a T1DHStandEnv).  others: every
     env's robot is drawn and casts shadows, not only the camera's own; terrain_shadow: the height field casts shadows.
-    With both off render() is t1render_frame; else t1render_scene, with the workspace allocated here, once."""
+    With both off render() is t1render_frame; else t1render_scene, with the workspace allocated here, once.  mesh (a
+    RobotMesh): render() is t1render_mesh_scene instead -- the robot is drawn as the mesh's triangles, prims is ignored,
+    and self.tris tells which triangle a pixel shows."""
 
-    def __init__(self, env, width, height, cameras, prims=None, style=None, others=False, terrain_shadow=False):
+    def __init__(self, env, width, height, cameras, prims=None, style=None, others=False, terrain_shadow=False,
+                 mesh=None):
         import torch
         self.env, self.width, self.height = env, int(width), int(height)
         self.cameras = list(cameras)
@@ -122,6 +177,9 @@ class Renderer:
             (_lib.RENDER_SCENE_TERRAIN_SHADOW if self.terrain_shadow else 0)
         # whose robot a pixel shows (-1: terrain, sky); stays -1 while both switches are off (t1render_frame has no such plane)
         self.envs = torch.full((n, self.height, self.width), -1, dtype=torch.int32, device=d)
+        self.mesh = mesh
+        # the caller's index of the triangle a pixel shows (-1: terrain, sky); written with a mesh only
+        self.tris = torch.full((n, self.height, self.width), -1, dtype=torch.int32, device=d) if mesh is not None else None
         self.workspace = None
         if self.others:
             size = env._lib.t1render_scene_workspace_bytes(int(env.num_envs), n)
@@ -132,7 +190,7 @@ class Renderer:
     def render(self, rgba_out=None):
         """On the current stream (one launch; with others a memset and three).  Returns the (ncams, H, W, 4) uint8
         device buffer it wrote: rgba_out when given (same shape, contiguous), else self.rgba; self.depth and self.ids
-        are written too, and self.envs whenever others or terrain_shadow is on."""
+        are written too, and self.envs whenever others or terrain_shadow is on (with a mesh: always, and self.tris)."""
         import torch
         out = self.rgba if rgba_out is None else rgba_out
         if rgba_out is not None and (out.shape != self.rgba.shape or out.dtype != torch.uint8 or
@@ -140,6 +198,15 @@ class Renderer:
             raise ValueError(f"rgba_out must be a contiguous uint8 {tuple(self.rgba.shape)} tensor on {self.rgba.device}")
         env = self.env
         stream = torch.cuda.current_stream(env.device).cuda_stream
+        if self.mesh is not None:
+            ws = self.workspace
+            _lib.check(env._lib.t1render_mesh_scene(env._handle, self._cams, len(self.cameras), self.mesh._handle,
+                                                    _lib.C.byref(self._style), self.flags, self.width, self.height,
+                                                    out.data_ptr(), self.depth.data_ptr(), self.ids.data_ptr(),
+                                                    self.envs.data_ptr(), self.tris.data_ptr(),
+                                                    ws.data_ptr() if ws is not None else None,
+                                                    ws.numel() if ws is not None else 0, stream), "t1render_mesh_scene")
+            return out
         if self.flags:
             ws = self.workspace
             _lib.check(env._lib.t1render_scene(env._handle, self._cams, len(self.cameras), self._prims, len(self.prims),

@@ -61,6 +61,24 @@ def box_corners(size, xyz, R):
     return c @ R.T + xyz
 
 
+def collapsed_parts(by_parent, name):
+    """The collapse rule: link ``name`` and every link that hangs on it through fixed joints only, as (link, p, R) with
+    p, R the link's frame in ``name``'s.  by_parent: parent link name -> its joint elements."""
+    parts = [(name, np.zeros(3), np.eye(3))]
+    stack = [(name, np.zeros(3), np.eye(3))]
+    while stack:
+        ln, p, R = stack.pop()
+        for j in by_parent.get(ln, []):
+            if j.get("type") != "fixed":
+                continue
+            xyz, Rj = _origin(j)
+            child = j.find("child").get("link")
+            item = (child, p + R @ xyz, R @ Rj)
+            parts.append(item)
+            stack.append(item)
+    return parts
+
+
 class Articulation:
     """Collapsed articulation.  Arrays are float64; ``pack()`` flattens them for the C-ABI."""
 
@@ -91,18 +109,7 @@ class Articulation:
                 self.joint_axis[b] = _vec(j.find("axis").get("xyz"))
                 self.parent[b] = BODY_NAMES.index(j.find("parent").get("link"))
             # merge this link and every fixed descendant into body b
-            parts = [(name, np.zeros(3), np.eye(3))]
-            stack = [(name, np.zeros(3), np.eye(3))]
-            while stack:
-                ln, p, R = stack.pop()
-                for j in by_parent.get(ln, []):
-                    if j.get("type") != "fixed":
-                        continue
-                    xyz, Rj = _origin(j)
-                    child = j.find("child").get("link")
-                    item = (child, p + R @ xyz, R @ Rj)
-                    parts.append(item)
-                    stack.append(item)
+            parts = collapsed_parts(by_parent, name)
             m_tot, mc = 0.0, np.zeros(3)
             pieces = []
             for ln, p, R in parts:
@@ -167,6 +174,45 @@ class Articulation:
             idx = np.nonzero(self.contact_body == b)[0]
             self.contact_count[b] = len(idx)
             self.contact_start[b] = idx[0] if len(idx) else 0
+
+
+def visual_meshes(urdf_path, missing_ok=False):
+    """Every <visual> mesh of the URDF in the frame of the collapsed body it belongs to: a dict of tri (T, 3, 3)
+    float32, body (T,) int32 (index into BODY_NAMES), link (T,) int32 (index into links), links (the names of the
+    links that contributed, in body order) and skipped (the mesh files left out).  Vertices go through the mesh's
+    scale, the visual's origin and the fixed-joint chain up to the body (collapsed_parts, the rule Articulation
+    applies to masses and inertias).  A missing mesh file raises FileNotFoundError naming it; with missing_ok the
+    visual is skipped and listed.  A visual that is not a mesh raises ValueError."""
+    root = ET.parse(urdf_path).getroot()
+    links = {l.get("name"): l for l in root.findall("link")}
+    by_parent = {}
+    for j in root.findall("joint"):
+        by_parent.setdefault(j.find("parent").get("link"), []).append(j)
+    mesh_dir = os.path.dirname(os.path.abspath(urdf_path))
+    tri, body, link, names, skipped = [], [], [], [], []
+    for b, name in enumerate(BODY_NAMES):
+        for ln, p, R in collapsed_parts(by_parent, name):
+            for vis in links[ln].findall("visual"):
+                g = vis.find("geometry")[0]
+                if g.tag != "mesh":
+                    raise ValueError(f"link {ln}: a {g.tag} visual is not a mesh")
+                path = os.path.normpath(os.path.join(mesh_dir, g.get("filename")))
+                if not os.path.exists(path):
+                    if not missing_ok:
+                        raise FileNotFoundError(f"link {ln}: visual mesh {path} not found")
+                    skipped.append(path)
+                    continue
+                vx, vR = _origin(vis)
+                v = load_stl(path).reshape(-1, 3) * _vec(g.get("scale") or "1 1 1")
+                v = (v @ vR.T + vx) @ R.T + p
+                if ln not in names:
+                    names.append(ln)
+                tri.append(v.reshape(-1, 3, 3))
+                body.append(np.full(len(v) // 3, b, np.int32))
+                link.append(np.full(len(v) // 3, names.index(ln), np.int32))
+    return dict(tri=np.concatenate(tri).astype(np.float32) if tri else np.zeros((0, 3, 3), np.float32),
+                body=np.concatenate(body) if body else np.zeros(0, np.int32),
+                link=np.concatenate(link) if link else np.zeros(0, np.int32), links=names, skipped=skipped)
 
 
 RESOURCE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "resources", "t1_model.json")
