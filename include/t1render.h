@@ -139,6 +139,47 @@ int t1render_mesh_scene(t1env* env, const t1render_camera* cams, int32_t ncams, 
                         uint32_t* rgba, float* depth, int32_t* ids, int32_t* envs, int32_t* tris,
                         void* workspace, long long workspace_bytes, void* stream);
 
+/* t1render_depth: the camera as a sensor.  One launch writes a depth image for EVERY env of the handle, each from a
+ * pinhole camera fixed to a body of that env's own robot, so the camera turns and pitches with the body.
+ *
+ * Pose of env n's camera: eye = p_b + R_b pos; forward f = R_b R_m e_x, left l = R_b R_m e_y, up u = R_b R_m e_z, with
+ * p_b = rigid_state[n][body][0:3], R_b the rotation of the quaternion rigid_state[n][body][3:7] by the formula above
+ * (t1render_mesh_scene), and R_m the rotation of the mount's quat by the same formula; the call normalises the sensor's
+ * quat on the host.  It is the pose rule of the top of this file: after a real-dynamics step rigid_state holds the
+ * post-physics, PRE-reset pose, and an env that was reset in that step is seen from where it fell.
+ * mounts: NULL, or device memory (num_envs, 7) float32, a pos and a UNIT quat (x, y, z, w) per env that replace the
+ * sensor's mount for that env (per-env randomisation of the mount); they are used as they are, not normalised.
+ *
+ * Ray of pixel (row i from the top, column j): x and y by the formula at the top of this file, direction
+ * d = normalize(f + x r + y u) with r = -l.  Scene of env n: the terrain by the rule above (the plane z = 0, or the height
+ * field restricted to its footprint and hit from either side), and env n's OWN robot, prims posed by rigid_state[n]; no
+ * other env's robot.  A primitive is hit where the ray enters it, so a primitive that contains the eye is not seen: the
+ * camera may sit inside the base's box.
+ *
+ * Value: the PLANAR depth z = t (d.f) of the nearest hit, t the distance along the unit direction, among the hits with
+ * near <= z <= far.  A primitive entered in front of the near plane is not seen, whatever of it lies behind the plane.
+ * Where there is no such hit (sky, beyond far, outside the footprint) the value is exactly far.  Ties: the terrain wins
+ * against a primitive, then the lower primitive index.  A hit's value is clamped to [near, far].
+ * depth: device memory (num_envs, height, width), fp32, or with T1RENDER_DEPTH_F16 fp16, the fp32 value rounded to
+ * nearest even.  ids: NULL, or device memory of the same shape, int8: -1 no hit in range, 0 terrain, 1 + body otherwise.
+ * ids == NULL changes no bit of depth.
+ *
+ * One launch on `stream` for every env of the handle, whatever their number; no allocation, no synchronisation, no host
+ * read, no write to any env buffer; sensor and prims are host memory read during the call and travel by value, so the
+ * call can be captured in a graph.
+ * Errors, all before any device work, outputs untouched.  T1ENV_E_ARG: a null env, sensor or depth; nprims outside
+ * [0, T1RENDER_MAXPRIM], or null prims with nprims > 0; the sensor's or a primitive's body outside [0, 13); a kind
+ * outside {0, 1}; width or height < 1; width * height * num_envs at or over 2^31; an unknown flag bit; vfov outside
+ * (0, pi); anything but 0 < near < far <= 200; a zero or non-finite quat; a non-finite pos.  T1ENV_E_STATE: a
+ * height-field env without terrain samples. */
+/* A pinhole depth camera fixed to body `body` of every env.  pos, quat (x, y, z, w): the camera's frame in the body's
+ * frame.  The camera looks along its own +x, +y is to its left, +z is up.  vfov: vertical field of view [rad]. */
+typedef struct t1render_sensor { int32_t body; float pos[3], quat[4], vfov, near, far; } t1render_sensor;
+#define T1RENDER_DEPTH_F16 1   /* depth is fp16: the fp32 value rounded to nearest even */
+int t1render_depth(t1env* env, const t1render_sensor* sensor, const float* mounts,
+                   const t1render_prim* prims, int32_t nprims, int32_t width, int32_t height, int32_t flags,
+                   void* depth, int8_t* ids, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,8 @@ RENDER_EXPORTS = ["t1render_frame"]
 RENDER_SCENE_EXPORTS = ["t1render_scene_workspace_bytes", "t1render_scene"]
 RENDER_MESH_EXPORTS = ["t1render_mesh_create", "t1render_mesh_destroy", "t1render_mesh_info",
                        "t1render_mesh_workspace_bytes", "t1render_mesh_scene"]
+RENDER_DEPTH_EXPORTS = ["t1render_depth"]   # the depth camera sensor: every env's mounted depth image in one launch
+RENDER_DEPTH_F16 = 1
 RENDER_SCENE_OTHERS, RENDER_SCENE_TERRAIN_SHADOW, RENDER_SCENE_BRUTE = 1, 2, 4
 RENDER_MESH_BRUTE = 8
 RENDER_MAXCAM, RENDER_MAXPRIM = 16, 32
@@ -132,6 +134,10 @@ class RenderPrim(C.Structure):
 
 class RenderStyle(C.Structure):
     _fields_ = [("light", f32 * 3), ("ambient", f32), ("terrain_rgb", (f32 * 3) * 2), ("sky_rgb", (f32 * 3) * 2)]
+
+
+class RenderSensor(C.Structure):
+    _fields_ = [("body", i32), ("pos", f32 * 3), ("quat", f32 * 4), ("vfov", f32), ("near", f32), ("far", f32)]
 
 
 _lib = None
@@ -210,6 +216,7 @@ def load():
         "t1render_mesh_workspace_bytes": ([i32, i32], C.c_longlong),
         "t1render_mesh_scene": ([vp, P(RenderCamera), i32, vp, P(RenderStyle), i32, i32, i32, vp, vp, vp, vp, vp,
                                  vp, C.c_longlong, vp], C.c_int),
+        "t1render_depth": ([vp, P(RenderSensor), vp, P(RenderPrim), i32, i32, i32, i32, vp, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

@@ -86,7 +86,7 @@ __device__ __forceinline__ void shade_pixel(const Scene& S, const RenderArgs& A,
   F3 n = f3(0, 0, 1);
   bool ground = false;
   if (A.hf) {
-    ground = cast_heightfield(A, o, d, best, n);
+    ground = cast_heightfield(A, o, d, T_MIN, best, n);
   } else if (d.z != 0.0f) {
     const float t = -o.z / d.z;
     if (t > T_MIN && t <= best) {

@@ -1,6 +1,6 @@
-// t1render_dev.h -- what the renderer's two units (t1render.hip: one robot per camera; t1render_scene.hip: every env's
-// robot, culled) share on the device: the kernel's view of the terrain and the call, the ray / primitive intersections,
-// the height field's walk and the colour packing.  Both units must see one text of these, so that a pixel of either
+// t1render_dev.h -- what the renderer's units (t1render.hip: one robot per camera; t1render_scene.hip: every env's
+// robot, culled; t1render_mesh.hip; t1render_depth.hip: every env's mounted depth sensor) share on the device: the kernel's view of the terrain and the call, the ray / primitive intersections,
+// the height field's walk and the colour packing.  All units must see one text of these, so that a pixel of any
 // kernel that meets the same primitives computes the same bits.
 #ifndef T1RENDER_DEV_H
 #define T1RENDER_DEV_H
@@ -109,12 +109,14 @@ __device__ __forceinline__ float box_entry(const WorldPrim& P, F3 o, F3 d, int& 
   return (miss || tn > tf) ? INFINITY : tn;
 }
 
-// The height field's nearest hit in (T_MIN, best]: true and best, n (the upward unit normal) updated.
-__device__ bool cast_heightfield(const RenderArgs& A, F3 o, F3 d, float& best, F3& n) {
+// The height field's nearest hit in (tmin, best]: true and best, n (the upward unit normal) updated.  Field: any view
+// with h, rows, cols, inv_hscale, vscale, border and z_top (RenderArgs; the depth sensor's narrower DepthArgs).
+template <class Field>
+__device__ bool cast_heightfield(const Field& A, F3 o, F3 d, float tmin, float& best, F3& n) {
   const float ih = A.inv_hscale;
   const float og[2] = {(o.x + A.border) * ih, (o.y + A.border) * ih}, dg[2] = {d.x * ih, d.y * ih};
   const int last[2] = {A.rows - 2, A.cols - 2};   // last cell of each axis
-  float t0 = T_MIN, t1 = best;
+  float t0 = tmin, t1 = best;
 #pragma unroll
   for (int k = 0; k < 2; ++k) {   // the footprint [0, rows-1] x [0, cols-1] in cells
     const float ext = (float)(last[k] + 1);
@@ -162,7 +164,7 @@ __device__ bool cast_heightfield(const RenderArgs& A, F3 o, F3 d, float& best, F
         const float u = u0 + t * dg[0], v = v0 + t * dg[1];
         const bool in = u >= -EDGE_TOL && u <= 1.0f + EDGE_TOL && v >= -EDGE_TOL && v <= 1.0f + EDGE_TOL &&
                         (tri == 0 ? u - v >= -EDGE_TOL : v - u >= -EDGE_TOL);
-        if (in && t > T_MIN && t <= best && t < tc) {
+        if (in && t > tmin && t <= best && t < tc) {
           tc = t;
           nc = f3(-a * ih, -b * ih, 1.0f);
         }

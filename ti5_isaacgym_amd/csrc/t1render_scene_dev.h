@@ -210,7 +210,7 @@ __device__ __forceinline__ Surface surface(const RenderArgs& R, F3 o, F3 d, floa
   const t1render_style& St = R.style;
   bool ground = false;
   if (R.hf) {
-    ground = cast_heightfield(R, o, d, best, h.n);
+    ground = cast_heightfield(R, o, d, T_MIN, best, h.n);
   } else if (d.z != 0.0f) {
     const float t = -o.z / d.z;
     if (t > T_MIN && t <= best) {
@@ -251,7 +251,7 @@ __device__ __forceinline__ void store_pixel(const SceneArgs& A, const Surface& h
   if (h.need && lit != 0.0f && (A.flags & T1RENDER_SCENE_TERRAIN_SHADOW) && R.hf) {
     float sb = T_MAX;
     F3 sn = f3(0, 0, 1);
-    if (cast_heightfield(R, h.so, f3(St.light[0], St.light[1], St.light[2]), sb, sn)) lit = 0.0f;
+    if (cast_heightfield(R, h.so, f3(St.light[0], St.light[1], St.light[2]), T_MIN, sb, sn)) lit = 0.0f;
   }
   const F3 col = h.sky ? h.col : (St.ambient + (1.0f - St.ambient) * h.nl * lit) * h.base;
   const size_t px_i = ((size_t)cam * R.height + i) * R.width + j;

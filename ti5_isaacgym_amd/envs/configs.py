@@ -36,6 +36,18 @@ class LeggedRobotCfg(BaseConfig):
         # "fp16" = BASELINE config 5's fp16 state (values computed in fp32 and rounded once)
         state_dtype = "fp32"
 
+        # build extension (not in the reference): a depth camera bolted to a body of every env's robot
+        # (utils/render.DepthSensor, t1render_depth).  enable: the env owns a sensor and returns its image in place as
+        # extras["depth"] (num_envs, height, width), rendered in reset() and after every update_interval-th step; off
+        # (the default) there is no key, no allocation and no launch.  pos / rpy: the mount in the body's frame (the
+        # camera looks along its +x; a positive pitch looks down) -- the repository knows no camera of the real robot,
+        # so this one, on the front of the base looking 0.6 rad down, is a placeholder to be replaced.
+        class depth_camera:
+            enable, update_interval = False, 1
+            width, height, body, vfov, near, far = 64, 48, 0, 0.9, 0.1, 3.0
+            pos, rpy = [0.1, 0.0, 0.1], [0.0, 0.6, 0.0]
+            dtype = "fp32"   # or "fp16"
+
     class terrain:
         mesh_type, horizontal_scale, vertical_scale, border_size, curriculum = "trimesh", 0.1, 0.005, 25, True
         static_friction, dynamic_friction, restitution, measure_heights = 1.0, 1.0, 0.0, False

@@ -261,9 +261,32 @@ class T1DHStandEnv(VecEnv):
         self.extras = {}
         self._ep_dicts = None
         self._slot = 0
+        self.depth_sensor, self._depth_interval = self._build_depth_sensor(), 1
+        if self.depth_sensor is not None:
+            self._depth_interval = int(cfg.env.depth_camera.update_interval)
         self.init_done = True
 
     # ------------------------------------------------------------------------------------------- setup
+    def _build_depth_sensor(self):
+        """cfg.env.depth_camera (configs.py): None unless enabled -- then the env's own utils/render.DepthSensor."""
+        dc = getattr(self.cfg.env, "depth_camera", None)
+        if dc is None or not dc.enable:
+            return None
+        if int(dc.update_interval) < 1:
+            raise ValueError(f"cfg.env.depth_camera.update_interval must be >= 1, got {dc.update_interval}")
+        if dc.dtype not in ("fp32", "fp16"):
+            raise ValueError(f"cfg.env.depth_camera.dtype must be 'fp32' or 'fp16', got {dc.dtype!r}")
+        import weakref
+        from ..utils.render import DepthSensor
+        # a proxy: env -> sensor -> env would be a cycle, and the handle of an env that only the cyclic collector frees is
+        # destroyed at whatever allocation triggers it, possibly inside somebody's graph capture
+        return DepthSensor(weakref.proxy(self), dc.width, dc.height, dc.pos, rpy=dc.rpy, body=dc.body, vfov=dc.vfov, near=dc.near,
+                           far=dc.far, dtype=torch.float16 if dc.dtype == "fp16" else torch.float32)
+
+    def _render_depth(self, s):
+        """One launch on the step's stream, after the step's own; extras["depth"] is the sensor's tensor, in place."""
+        self.extras["depth"] = self.depth_sensor.render(s)
+
     def _alloc(self, N):
         d, f, i64, i32, b = self.device, torch.float32, torch.int64, torch.int32, torch.bool
         z = lambda *s, dtype=f: torch.zeros(*s, dtype=dtype, device=d)  # noqa: E731
@@ -624,6 +647,8 @@ class T1DHStandEnv(VecEnv):
         self.common_step_counter += 1
         self._slot ^= 1
         self._fill_extras(self.common_step_counter % EXTRAS_RING)
+        if self.depth_sensor is not None and self.common_step_counter % self._depth_interval == 0:
+            self._render_depth(s)
         return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
 
     def _fill_extras(self, slot):
@@ -681,6 +706,8 @@ class T1DHStandEnv(VecEnv):
         """LeggedRobot.reset (legged_robot.py:450-455)."""
         self.reset_idx_all()
         obs, priv, _, _, _ = self.step(torch.zeros(self.num_envs, self.num_actions, device=self.device))
+        if self.depth_sensor is not None and self.common_step_counter % self._depth_interval != 0:
+            self._render_depth(self._stream())   # off the update interval too: a reset leaves a current image
         return obs, priv
 
     def set_fused(self, enable=True):

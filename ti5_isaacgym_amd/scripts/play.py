@@ -5,6 +5,8 @@ joystick, its camera as --render: DESIGN.md §9).
         [--command VX VY YAW] [--state_dtype fp32|fp16] [--robot_index 0] [--out DIR]
         [--render DIR [--render_every 2] [--render_size 640 360] [--render_follow 3.0 0.0 1.0]
                       [--render_scene own|all] [--render_terrain_shadow] [--render_urdf PATH]]
+        [--depth DIR [--depth_size 64 48] [--depth_every 2] [--depth_mount X Y Z ROLL PITCH YAW]
+                     [--depth_range 0.1 3.0]]
 
 The reference play's config changes (episode_length_s 1000, the noise curriculum off), its loop -- the deterministic
 policy (DHOnPolicyRunner.get_inference_policy(graphed=True): the first conv and the actor kernel as one replayed HIP
@@ -25,6 +27,13 @@ summary.json then also counts the last frame's "robot_pixels".  The repository s
 robot description.  Every --render_every-th step is rendered into one preallocated
 device buffer and written as DIR/frame_%06d.png after the loop; summary.json then also counts the "frames".  Nothing
 here encodes video: e.g. ffmpeg -framerate 50 -i DIR/frame_%06d.png -pix_fmt yuv420p play.mp4.
+
+With --depth DIR a depth camera sensor is bolted to every env's base (utils/render.DepthSensor: one launch draws all
+envs) at --depth_mount, the position and roll, pitch, yaw of the camera in the base's frame (it looks along its +x; a
+positive pitch looks down; the default is a placeholder, the repository knows no camera of the real robot).  After every
+--depth_every-th step the image of --robot_index is kept in a preallocated device buffer; after the loop they are
+written as DIR/depth.npy ((frames, H, W) float16, planar depth in metres, --depth_range's FAR where nothing is in
+range) and as grey DIR/depth_%06d.png (near white, far black); summary.json then also counts the "depth_frames".
 
 Every logged value stays in device buffers until the run ends: no host read per step.
 """
@@ -64,8 +73,15 @@ def parse(argv=None):
     p.add_argument("--render_scene", choices=["own", "all"], default="own")
     p.add_argument("--render_terrain_shadow", action="store_true")
     p.add_argument("--render_urdf", default=None, metavar="PATH")
+    p.add_argument("--depth", default=None, metavar="DIR")
+    p.add_argument("--depth_size", type=int, nargs=2, default=[64, 48], metavar=("W", "H"))
+    p.add_argument("--depth_every", type=int, default=2, metavar="K")
+    p.add_argument("--depth_mount", type=float, nargs=6, default=[0.1, 0.0, 0.1, 0.0, 0.6, 0.0],
+                   metavar=("X", "Y", "Z", "ROLL", "PITCH", "YAW"))
+    p.add_argument("--depth_range", type=float, nargs=2, default=[0.1, 3.0], metavar=("NEAR", "FAR"))
     a = p.parse_args(argv)
     check_render_args(a)
+    check_depth_args(a)
     return a
 
 
@@ -95,6 +111,24 @@ def check_render_args(a):
         raise ValueError(f"--render: {frames} frames of {w} x {h} pixels need {frames * w * h * 4 / 2 ** 30:.1f} GiB of "
                          "device memory, more than the 8 GiB frame buffer; raise --render_every, lower --steps or "
                          "--render_size")
+
+
+def check_depth_args(a):
+    """Refuse a --depth run with --depth_every or a size below 1, a range that is not 0 < NEAR < FAR <= 200, or a frame
+    buffer (frames x width x height x 2 bytes) over 8 GiB, before any device work."""
+    if a.depth is None:
+        return
+    w, h = a.depth_size
+    if a.depth_every < 1 or w < 1 or h < 1:
+        raise ValueError(f"--depth_every {a.depth_every} and --depth_size {w} {h} must be >= 1")
+    near, far = a.depth_range
+    if not 0.0 < near < far <= 200.0:
+        raise ValueError(f"--depth_range {near} {far}: need 0 < NEAR < FAR <= 200")
+    frames = num_frames(a.steps, a.depth_every)
+    if frames * w * h * 2 > MAX_FRAME_BYTES:
+        raise ValueError(f"--depth: {frames} frames of {w} x {h} pixels need {frames * w * h * 2 / 2 ** 30:.1f} GiB of "
+                         "device memory, more than the 8 GiB frame buffer; raise --depth_every, lower --steps or "
+                         "--depth_size")
 
 
 def main(argv=None):
@@ -133,6 +167,13 @@ def main(argv=None):
         renderer = Renderer(env, w, h, [Camera.follow(r, offset=tuple(a.render_follow))],
                             others=a.render_scene == "all", terrain_shadow=a.render_terrain_shadow, mesh=mesh)
         frames = torch.zeros(num_frames(T, a.render_every), 1, h, w, 4, dtype=torch.uint8, device=dev)
+    sensor = depth_frames = None
+    if a.depth is not None:
+        from ti5_isaacgym_amd.utils.render import DepthSensor, write_png
+        dw, dh = a.depth_size
+        sensor = DepthSensor(env, dw, dh, a.depth_mount[:3], rpy=a.depth_mount[3:], near=a.depth_range[0],
+                             far=a.depth_range[1], dtype=torch.float16)
+        depth_frames = torch.zeros(num_frames(T, a.depth_every), dh, dw, dtype=torch.float16, device=dev)
     obs = env.get_observations()
     with torch.inference_mode():
         for i in range(T):
@@ -147,6 +188,8 @@ def main(argv=None):
             joints[i] = torch.stack((actions[r] * scale, env.dof_pos[r], env.dof_vel[r], env.torques[r]))
             if renderer is not None and (i + 1) % a.render_every == 0:
                 renderer.render(frames[(i + 1) // a.render_every - 1])
+            if sensor is not None and (i + 1) % a.depth_every == 0:
+                depth_frames[(i + 1) // a.depth_every - 1].copy_(sensor.render()[r])
             ep = infos.get("episode") or {}
             if ep_keys is None:
                 ep_keys = [k for k, v in ep.items() if isinstance(v, torch.Tensor)]
@@ -179,6 +222,16 @@ def main(argv=None):
         print(f"wrote {images.shape[0]} frames to {a.render}; a video: ffmpeg -framerate "
               f"{1.0 / (float(env.dt) * a.render_every):g} -i {os.path.join(a.render, 'frame_%06d.png')} "
               "-pix_fmt yuv420p play.mp4")
+    if sensor is not None:
+        os.makedirs(a.depth, exist_ok=True)
+        images = depth_frames.cpu().numpy()
+        np.save(os.path.join(a.depth, "depth.npy"), images)
+        near, far = sensor.near, sensor.far
+        grey = np.floor(np.clip((far - images.astype(np.float32)) / (far - near), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+        for k in range(images.shape[0]):
+            write_png(os.path.join(a.depth, "depth_%06d.png" % k), np.repeat(grey[k][:, :, None], 3, axis=2))
+        summary["depth_frames"] = int(images.shape[0])
+        print(f"wrote {images.shape[0]} depth images to {a.depth}")
     with open(os.path.join(a.out, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     print(json.dumps(summary))

@@ -14,6 +14,12 @@ primitives (t1render_mesh_scene: a bounding volume hierarchy per body, walked on
 triangle a pixel shows); smooth shading, textures and materials are not drawn.  After a
 real-dynamics step ``rigid_state`` holds the post-physics, pre-reset pose, so an env reset in that step is drawn where
 it fell.
+
+The camera as a sensor is ``DepthSensor``: one launch (t1render_depth, csrc/t1render_depth.hip) writes a small depth
+image for every env, from a camera mounted on a body of the env's own robot.
+
+    s = DepthSensor(env, 64, 48, pos=(0.1, 0.0, 0.1), rpy=(0.0, 0.6, 0.0))
+    depth = s.render()              # (num_envs, 48, 64) float32 on the device, planar depth in [near, far]
 """
 import struct
 import zlib
@@ -219,6 +225,70 @@ class Renderer:
                                            _lib.C.byref(self._style), self.width, self.height, out.data_ptr(),
                                            self.depth.data_ptr(), self.ids.data_ptr(), stream), "t1render_frame")
         return out
+
+
+def rpy_quat(roll, pitch, yaw):
+    """The quaternion (x, y, z, w) of the rotation Rz(yaw) Ry(pitch) Rx(roll) (a URDF's rpy): a positive pitch turns the
+    camera's +x towards -z, i.e. looks down."""
+    cr, sr, cp, sp, cy, sy = (f(0.5 * a) for a in (roll, pitch, yaw) for f in (np.cos, np.sin))
+    return (float(sr * cp * cy - cr * sp * sy), float(cr * sp * cy + sr * cp * sy),
+            float(cr * cp * sy - sr * sp * cy), float(cr * cp * cy + sr * sp * sy))
+
+
+class DepthSensor:
+    """A depth camera bolted to body ``body`` of every env's robot (t1render_depth): one launch writes
+    ``self.depth`` (num_envs, height, width), the planar depth [m] of the nearest surface in [near, far] and exactly
+    ``far`` where there is none, for all envs of ``env`` (a T1DHStandEnv) at once.
+
+    pos, and quat (x, y, z, w) or rpy (roll, pitch, yaw; at most one of the two, default: none, the body's own axes):
+    the camera's frame in the body's frame; it looks along its +x, +y is to its left, +z is up.  pos has no default:
+    the repository knows no camera of the real robot, so the mount is the caller's to state.  The scene of an env is
+    the terrain and its own robot as ``prims`` (None: robot_primitives()); a primitive that contains the camera is not
+    seen, so the mount may lie inside the base's box.  dtype: torch.float32 (also what None means: this module imports
+    torch only where it needs it), or torch.float16 (the fp32 value rounded once).  ids=True also allocates ``self.ids`` (int8: -1 nothing in range, 0 terrain, 1 + body).  mounts: None, or a
+    (num_envs, 7) float32 device tensor of pos and unit quat per env that replaces the mount env by env (kept by
+    reference: write into it to re-randomise).  After a real-dynamics step an env that was reset is seen from where it
+    fell (rigid_state holds the pre-reset pose)."""
+
+    def __init__(self, env, width, height, pos, quat=None, rpy=None, body=0, vfov=DEFAULT_VFOV, near=0.1, far=3.0,
+                 dtype=None, prims=None, ids=False, mounts=None):
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        if dtype not in (torch.float32, torch.float16):
+            raise ValueError(f"DepthSensor writes torch.float32 or torch.float16, got {dtype}")
+        if quat is not None and rpy is not None:
+            raise ValueError("DepthSensor takes quat or rpy, not both")
+        quat = rpy_quat(*rpy) if rpy is not None else (0.0, 0.0, 0.0, 1.0) if quat is None else quat
+        self.env, self.width, self.height = env, int(width), int(height)
+        self.prims = list(robot_primitives() if prims is None else prims)
+        if len(self.prims) > _lib.RENDER_MAXPRIM:
+            raise ValueError(f"at most {_lib.RENDER_MAXPRIM} primitives, got {len(self.prims)}")
+        self.near, self.far = float(near), float(far)
+        self._sensor = _lib.RenderSensor(int(body), (_lib.f32 * 3)(*[float(x) for x in pos]),
+                                         (_lib.f32 * 4)(*[float(x) for x in quat]), float(vfov), self.near, self.far)
+        self._prims = pack_prims(self.prims)
+        self.flags = _lib.RENDER_DEPTH_F16 if dtype == torch.float16 else 0
+        n, d = int(env.num_envs), env.device
+        if mounts is not None and (tuple(mounts.shape) != (n, 7) or mounts.dtype != torch.float32 or
+                                   not mounts.is_contiguous() or mounts.device != d):
+            raise ValueError(f"mounts must be a contiguous float32 ({n}, 7) tensor on {d}")
+        self.mounts = mounts
+        self.depth = torch.zeros(n, self.height, self.width, dtype=dtype, device=d)
+        self.ids = torch.zeros(n, self.height, self.width, dtype=torch.int8, device=d) if ids else None
+
+    def render(self, stream=None):
+        """One launch on ``stream`` (a raw stream handle; None: torch's current stream of the env's device), no
+        allocation.  Returns self.depth; self.ids is written too when it exists."""
+        env = self.env
+        if stream is None:
+            import torch
+            stream = torch.cuda.current_stream(env.device).cuda_stream
+        _lib.check(env._lib.t1render_depth(env._handle, _lib.C.byref(self._sensor),
+                                           self.mounts.data_ptr() if self.mounts is not None else None, self._prims,
+                                           len(self.prims), self.width, self.height, self.flags, self.depth.data_ptr(),
+                                           self.ids.data_ptr() if self.ids is not None else None, stream),
+                   "t1render_depth")
+        return self.depth
 
 
 def write_png(path, hwc_uint8):
