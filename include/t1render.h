@@ -180,6 +180,60 @@ int t1render_depth(t1env* env, const t1render_sensor* sensor, const float* mount
                    const t1render_prim* prims, int32_t nprims, int32_t width, int32_t height, int32_t flags,
                    void* depth, int8_t* ids, void* stream);
 
+/* t1render_depth_model: what a real stereo depth camera makes of the clean image -- noise that grows with the square of
+ * the depth, pixels without a measurement (random dropouts, and the occlusion shadow on the far side of a depth edge),
+ * and a per-env latency served from a ring of the last K measured frames.  A function of device arrays only: no env
+ * handle.  One launch on `stream`; no allocation, no synchronisation, no host read; m is host memory read during the
+ * call and travels by value, so the call can be captured in a graph (frame is then the captured one).
+ *
+ * clean: device memory (num_envs, height, width), fp32, or with T1RENDER_DEPTH_F16 fp16 (ring and out then too), as
+ * t1render_depth writes it; it is only read.  Measured pixel of env e, row i, column j, from z, the clean value as
+ * fp32.  Every operation below is one fp32 operation rounded to nearest, in the order written, none fused.
+ *   Draws: h_k = hash4(seed, env_base + e, frame, 4 (i width + j) + k), k = 0..3, the 32-bit counter hash of the env
+ *   step (csrc/t1_common.h; all arguments mod 2^32), and u_k = (h_k >> 8) 2^-24 in [0, 1).
+ *   1. Nothing in range: z >= far gives fill.
+ *   2. Dropout: u_0 < p_drop gives fill.
+ *   3. Edge shadow, only with p_edge != 0 (with p_edge == 0 no neighbour is read): mn is the smallest clean value among
+ *      the pixels (i-1, j), (i+1, j), (i, j-1), (i, j+1) that lie inside the image (a 1 x 1 image has none: no shadow).
+ *      z - mn > edge_abs + edge_rel mn and u_1 < p_edge gives fill: the pixel is on the far side of an occlusion edge.
+ *   4. Noise: s = (h_2 & 0xFFFF) + (h_2 >> 16) + (h_3 & 0xFFFF) + (h_3 >> 16) - 131070, an integer in [-131070, 131070];
+ *      g = (float)s c with c = sqrt(3) / 65536 rounded to fp32 (an Irwin-Hall sum of four: mean 0, variance 1 to within
+ *      3e-10, |g| <= 3.4641).  The value is min(max(z + (sigma0 + (sigma2 z) z) g, near), far).
+ *   5. The value, or fill, is stored as fp32, or rounded to nearest even to fp16 (fill too: choose one fp16 can hold).
+ *
+ * Ring and delay.  ring: device memory (ring_frames, num_envs, height, width) = K frames, owned by the caller and only
+ * written by this call.  The measured pixel goes to slot frame mod K, and to all K slots of an env with fresh[e] != 0.
+ * out[e] (the shape of clean) is the ring's frame of slot (frame - d) mod K (the true residue, also while frame < d),
+ * d = min(max(lag[e], 0), K - 1): what was measured d calls ago, given that the caller counts frame up by one per
+ * call.  lag: NULL (no delay), or device int32 (num_envs); fresh: NULL (none), or device uint8 (num_envs).  A fresh env
+ * has no history: all its slots hold this call's frame, so for the next K - 1 calls it is served nothing older.  THE
+ * CALLER MUST MAKE EVERY ENV FRESH ON THE FIRST CALL (and an env whenever its history ends, e.g. after a reset): the
+ * ring's content before that is never looked at, and without it the call serves whatever the memory held.  With K == 1
+ * there is no delay, ring may be NULL and the call is the noise pass alone (a non-NULL ring still gets its one slot).
+ * frame counts calls and is meant to stay below 2^32; same inputs and same frame give the same bits.
+ *
+ * Errors, all before any device work, outputs and ring untouched, T1ENV_E_ARG: a null m, clean or out; a null ring with
+ * ring_frames > 1; ring_frames outside [1, 16]; num_envs, width or height < 1; width * height * num_envs at or over
+ * 2^31; an unknown flag bit; anything but 0 < near < far <= 200; p_drop or p_edge outside [0, 1] (or not a number); a
+ * negative or non-finite sigma0, sigma2, edge_abs or edge_rel; a non-finite fill; clean, ring or out off the
+ * alignment of its element (4 bytes, 2 with T1RENDER_DEPTH_F16); out or ring overlapping clean, or each other. */
+typedef struct t1render_depth_noise {
+  uint32_t seed;        /* the sensor's own seed; keep it apart from the env step's, whose draws share the hash */
+  int32_t  env_base;    /* added to the env index in every draw (a rank's first global env) */
+  float near, far;      /* the clean image's range */
+  float sigma0, sigma2; /* noise std [m]: sigma0 + sigma2 * z * z  (stereo: grows with z^2) */
+  float p_drop;         /* per-pixel dropout probability */
+  float p_edge, edge_abs, edge_rel; /* occlusion-shadow dropout at depth edges */
+  float fill;           /* value of a pixel without a measurement (any finite float) */
+} t1render_depth_noise;
+#define T1RENDER_DEPTH_MAXRING 16
+int t1render_depth_model(const t1render_depth_noise* m, const void* clean, int32_t num_envs,
+                         int32_t width, int32_t height, int32_t flags /* T1RENDER_DEPTH_F16: clean, ring, out are fp16 */,
+                         uint32_t frame, void* ring, int32_t ring_frames /* K, 1..16 */,
+                         const int32_t* lag /* (num_envs) or NULL = 0 */,
+                         const uint8_t* fresh /* (num_envs) or NULL = none */,
+                         void* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

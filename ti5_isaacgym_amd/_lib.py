@@ -118,7 +118,10 @@ RENDER_SCENE_EXPORTS = ["t1render_scene_workspace_bytes", "t1render_scene"]
 RENDER_MESH_EXPORTS = ["t1render_mesh_create", "t1render_mesh_destroy", "t1render_mesh_info",
                        "t1render_mesh_workspace_bytes", "t1render_mesh_scene"]
 RENDER_DEPTH_EXPORTS = ["t1render_depth"]   # the depth camera sensor: every env's mounted depth image in one launch
+# the sensor model behind it: noise, dropouts and a per-env latency ring, a function of device arrays only
+RENDER_DEPTH_MODEL_EXPORTS = ["t1render_depth_model"]
 RENDER_DEPTH_F16 = 1
+RENDER_DEPTH_MAXRING = 16
 RENDER_SCENE_OTHERS, RENDER_SCENE_TERRAIN_SHADOW, RENDER_SCENE_BRUTE = 1, 2, 4
 RENDER_MESH_BRUTE = 8
 RENDER_MAXCAM, RENDER_MAXPRIM = 16, 32
@@ -138,6 +141,11 @@ class RenderStyle(C.Structure):
 
 class RenderSensor(C.Structure):
     _fields_ = [("body", i32), ("pos", f32 * 3), ("quat", f32 * 4), ("vfov", f32), ("near", f32), ("far", f32)]
+
+
+class RenderDepthNoise(C.Structure):
+    _fields_ = [("seed", u32), ("env_base", i32), ("near", f32), ("far", f32), ("sigma0", f32), ("sigma2", f32),
+                ("p_drop", f32), ("p_edge", f32), ("edge_abs", f32), ("edge_rel", f32), ("fill", f32)]
 
 
 _lib = None
@@ -217,6 +225,7 @@ def load():
         "t1render_mesh_scene": ([vp, P(RenderCamera), i32, vp, P(RenderStyle), i32, i32, i32, vp, vp, vp, vp, vp,
                                  vp, C.c_longlong, vp], C.c_int),
         "t1render_depth": ([vp, P(RenderSensor), vp, P(RenderPrim), i32, i32, i32, i32, vp, vp, vp], C.c_int),
+        "t1render_depth_model": ([P(RenderDepthNoise), vp, i32, i32, i32, i32, u32, vp, i32, vp, vp, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)

@@ -47,6 +47,15 @@ class LeggedRobotCfg(BaseConfig):
             width, height, body, vfov, near, far = 64, 48, 0, 0.9, 0.1, 3.0
             pos, rpy = [0.1, 0.0, 0.1], [0.0, 0.6, 0.0]
             dtype = "fp32"   # or "fp16"
+            # the sensor model (utils/render.DepthNoise, t1render_depth_model): with noise.enable or a non-zero
+            # latency_frames, extras["depth"] is the MEASURED image -- depth-squared noise, dropouts, occlusion
+            # shadows, and env n's image delayed by a number of renders drawn once in [lo, hi] -- seeded by cfg.seed;
+            # an env's first image after its reset never shows its previous episode.  Off (the default): the clean one.
+            latency_frames = [0, 0]
+
+            class noise:
+                enable = False
+                sigma0, sigma2, p_drop, p_edge, edge_abs, edge_rel, fill = 0.0, 0.0, 0.0, 0.0, 0.05, 0.05, None
 
     class terrain:
         mesh_type, horizontal_scale, vertical_scale, border_size, curriculum = "trimesh", 0.1, 0.005, 25, True

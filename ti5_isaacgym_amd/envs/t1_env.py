@@ -261,6 +261,7 @@ class T1DHStandEnv(VecEnv):
         self.extras = {}
         self._ep_dicts = None
         self._slot = 0
+        self._depth_fresh = None
         self.depth_sensor, self._depth_interval = self._build_depth_sensor(), 1
         if self.depth_sensor is not None:
             self._depth_interval = int(cfg.env.depth_camera.update_interval)
@@ -277,15 +278,32 @@ class T1DHStandEnv(VecEnv):
         if dc.dtype not in ("fp32", "fp16"):
             raise ValueError(f"cfg.env.depth_camera.dtype must be 'fp32' or 'fp16', got {dc.dtype!r}")
         import weakref
-        from ..utils.render import DepthSensor
+        from ..utils.render import DepthNoise, DepthSensor
+        nz, lat = getattr(dc, "noise", None), tuple(getattr(dc, "latency_frames", (0, 0)))
+        noise = None
+        if nz is not None and nz.enable:
+            noise = DepthNoise(nz.sigma0, nz.sigma2, nz.p_drop, nz.p_edge, nz.edge_abs, nz.edge_rel, nz.fill)
+        # the envs reset since the last render (the model's `fresh`): kept only with a model
+        if noise is not None or lat != (0, 0):
+            self._depth_fresh = torch.ones(self.num_envs, dtype=torch.uint8, device=self.device)
         # a proxy: env -> sensor -> env would be a cycle, and the handle of an env that only the cyclic collector frees is
         # destroyed at whatever allocation triggers it, possibly inside somebody's graph capture
         return DepthSensor(weakref.proxy(self), dc.width, dc.height, dc.pos, rpy=dc.rpy, body=dc.body, vfov=dc.vfov, near=dc.near,
-                           far=dc.far, dtype=torch.float16 if dc.dtype == "fp16" else torch.float32)
+                           far=dc.far, dtype=torch.float16 if dc.dtype == "fp16" else torch.float32, noise=noise,
+                           latency=lat, seed=int(getattr(self.cfg, "seed", 5)), env_base=self.env_offset)
 
     def _render_depth(self, s):
-        """One launch on the step's stream, after the step's own; extras["depth"] is the sensor's tensor, in place."""
-        self.extras["depth"] = self.depth_sensor.render(s)
+        """One launch on the step's stream, after the step's own (two with the sensor model); extras["depth"] is the
+        sensor's tensor, in place.  With a model the render consumes the mask of the envs reset since the last one."""
+        self.extras["depth"] = self.depth_sensor.render(s, self._depth_fresh)
+        if self._depth_fresh is not None:
+            self._depth_fresh.zero_()
+
+    def _note_depth_resets(self):
+        """After a step (and its render, which showed the pre-reset pose): the envs it reset are fresh at the next
+        render.  In place on the step's stream; no allocation, no host read."""
+        if self._depth_fresh is not None:
+            self._depth_fresh.bitwise_or_(self.reset_buf.view(torch.uint8))
 
     def _alloc(self, N):
         d, f, i64, i32, b = self.device, torch.float32, torch.int64, torch.int32, torch.bool
@@ -647,8 +665,10 @@ class T1DHStandEnv(VecEnv):
         self.common_step_counter += 1
         self._slot ^= 1
         self._fill_extras(self.common_step_counter % EXTRAS_RING)
-        if self.depth_sensor is not None and self.common_step_counter % self._depth_interval == 0:
-            self._render_depth(s)
+        if self.depth_sensor is not None:
+            if self.common_step_counter % self._depth_interval == 0:
+                self._render_depth(s)
+            self._note_depth_resets()
         return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
 
     def _fill_extras(self, slot):
@@ -676,6 +696,8 @@ class T1DHStandEnv(VecEnv):
             self._command_curriculum(float(self.episode_sums["tracking_lin_vel"].sum()), float(self.num_envs))
         a = self._args(self.common_step_counter)
         _lib.check(self._lib.t1env_reset_all(self._handle, _lib.C.byref(a), self._stream()), "t1env_reset_all")
+        if self._depth_fresh is not None:
+            self._depth_fresh.fill_(1)
         if self.measure_heights:   # reset_idx clears the critic history deque (t1_dh_stand_env.py:548-558)
             for t in self._priv_ext:
                 t.zero_()
@@ -698,13 +720,15 @@ class T1DHStandEnv(VecEnv):
         a.obs_slot = self._slot ^ 1   # the buffer holding the current observations
         _lib.check(self._lib.t1env_reset_idx(self._handle, _ptr(mask), _lib.C.byref(a), self._stream()),
                    "t1env_reset_idx")
+        if self._depth_fresh is not None:
+            self._depth_fresh.bitwise_or_(mask)
         if self.measure_heights:
             self._priv_ext[self._slot ^ 1][ids] = 0.0
         self._fill_extras(self.common_step_counter % EXTRAS_RING)
 
     def reset(self):
         """LeggedRobot.reset (legged_robot.py:450-455)."""
-        self.reset_idx_all()
+        self.reset_idx_all()   # marks every env fresh: the render below serves no older image
         obs, priv, _, _, _ = self.step(torch.zeros(self.num_envs, self.num_actions, device=self.device))
         if self.depth_sensor is not None and self.common_step_counter % self._depth_interval != 0:
             self._render_depth(self._stream())   # off the update interval too: a reset leaves a current image

@@ -6,7 +6,7 @@ joystick, its camera as --render: DESIGN.md §9).
         [--render DIR [--render_every 2] [--render_size 640 360] [--render_follow 3.0 0.0 1.0]
                       [--render_scene own|all] [--render_terrain_shadow] [--render_urdf PATH]]
         [--depth DIR [--depth_size 64 48] [--depth_every 2] [--depth_mount X Y Z ROLL PITCH YAW]
-                     [--depth_range 0.1 3.0]]
+                     [--depth_range 0.1 3.0] [--depth_noise] [--depth_latency LO HI]]
 
 The reference play's config changes (episode_length_s 1000, the noise curriculum off), its loop -- the deterministic
 policy (DHOnPolicyRunner.get_inference_policy(graphed=True): the first conv and the actor kernel as one replayed HIP
@@ -34,6 +34,9 @@ positive pitch looks down; the default is a placeholder, the repository knows no
 --depth_every-th step the image of --robot_index is kept in a preallocated device buffer; after the loop they are
 written as DIR/depth.npy ((frames, H, W) float16, planar depth in metres, --depth_range's FAR where nothing is in
 range) and as grey DIR/depth_%06d.png (near white, far black); summary.json then also counts the "depth_frames".
+--depth_noise puts the sensor model behind it (utils/render.DepthNoise with DEPTH_NOISE below: depth-squared noise,
+dropouts and occlusion shadows, a pixel without a measurement reading FAR) and --depth_latency LO HI serves every env's
+image a number of depth frames late, drawn once per env in [LO, HI]; the images written are then the measured ones.
 
 Every logged value stays in device buffers until the run ends: no host read per step.
 """
@@ -79,6 +82,8 @@ def parse(argv=None):
     p.add_argument("--depth_mount", type=float, nargs=6, default=[0.1, 0.0, 0.1, 0.0, 0.6, 0.0],
                    metavar=("X", "Y", "Z", "ROLL", "PITCH", "YAW"))
     p.add_argument("--depth_range", type=float, nargs=2, default=[0.1, 3.0], metavar=("NEAR", "FAR"))
+    p.add_argument("--depth_noise", action="store_true")
+    p.add_argument("--depth_latency", type=int, nargs=2, default=[0, 0], metavar=("LO", "HI"))
     a = p.parse_args(argv)
     check_render_args(a)
     check_depth_args(a)
@@ -86,6 +91,10 @@ def parse(argv=None):
 
 
 MAX_FRAME_BYTES = 8 << 30
+# --depth_noise: a stereo camera's order of magnitude (2 mm + 5 mm/m^2: 4.7 cm at 3 m; 1 % dropouts; every second pixel
+# of an occlusion shadow lost) -- a placeholder like the mount, to be replaced by the real sensor's figures
+DEPTH_NOISE = dict(sigma0=0.002, sigma2=0.005, p_drop=0.01, p_edge=0.5)
+MAX_DEPTH_LATENCY = 15
 
 
 def num_frames(steps, every):
@@ -115,9 +124,15 @@ def check_render_args(a):
 
 def check_depth_args(a):
     """Refuse a --depth run with --depth_every or a size below 1, a range that is not 0 < NEAR < FAR <= 200, or a frame
-    buffer (frames x width x height x 2 bytes) over 8 GiB, before any device work."""
+    buffer (frames x width x height x 2 bytes) over 8 GiB, before any device work; --depth_noise or --depth_latency
+    without --depth, and a latency that is not 0 <= LO <= HI <= 15, likewise."""
+    lo, hi = a.depth_latency
     if a.depth is None:
+        if a.depth_noise or (lo, hi) != (0, 0):
+            raise ValueError("--depth_noise and --depth_latency need --depth DIR")
         return
+    if not 0 <= lo <= hi <= MAX_DEPTH_LATENCY:
+        raise ValueError(f"--depth_latency {lo} {hi}: need 0 <= LO <= HI <= {MAX_DEPTH_LATENCY}")
     w, h = a.depth_size
     if a.depth_every < 1 or w < 1 or h < 1:
         raise ValueError(f"--depth_every {a.depth_every} and --depth_size {w} {h} must be >= 1")
@@ -169,10 +184,13 @@ def main(argv=None):
         frames = torch.zeros(num_frames(T, a.render_every), 1, h, w, 4, dtype=torch.uint8, device=dev)
     sensor = depth_frames = None
     if a.depth is not None:
-        from ti5_isaacgym_amd.utils.render import DepthSensor, write_png
+        from ti5_isaacgym_amd.utils.render import DepthNoise, DepthSensor, write_png
         dw, dh = a.depth_size
         sensor = DepthSensor(env, dw, dh, a.depth_mount[:3], rpy=a.depth_mount[3:], near=a.depth_range[0],
-                             far=a.depth_range[1], dtype=torch.float16)
+                             far=a.depth_range[1], dtype=torch.float16,
+                             noise=DepthNoise(**DEPTH_NOISE) if a.depth_noise else None,
+                             latency=tuple(a.depth_latency), seed=a.seed)
+        depth_fresh = torch.zeros(a.num_envs, dtype=torch.uint8, device=dev)   # the envs reset since the last image
         depth_frames = torch.zeros(num_frames(T, a.depth_every), dh, dw, dtype=torch.float16, device=dev)
     obs = env.get_observations()
     with torch.inference_mode():
@@ -188,8 +206,11 @@ def main(argv=None):
             joints[i] = torch.stack((actions[r] * scale, env.dof_pos[r], env.dof_vel[r], env.torques[r]))
             if renderer is not None and (i + 1) % a.render_every == 0:
                 renderer.render(frames[(i + 1) // a.render_every - 1])
-            if sensor is not None and (i + 1) % a.depth_every == 0:
-                depth_frames[(i + 1) // a.depth_every - 1].copy_(sensor.render()[r])
+            if sensor is not None:
+                if (i + 1) % a.depth_every == 0:
+                    depth_frames[(i + 1) // a.depth_every - 1].copy_(sensor.render(fresh=depth_fresh)[r])
+                    depth_fresh.zero_()
+                depth_fresh.bitwise_or_(dones.view(torch.uint8))   # seen from where it fell now, fresh at the next image
             ep = infos.get("episode") or {}
             if ep_keys is None:
                 ep_keys = [k for k, v in ep.items() if isinstance(v, torch.Tensor)]

@@ -20,6 +20,11 @@ image for every env, from a camera mounted on a body of the env's own robot.
 
     s = DepthSensor(env, 64, 48, pos=(0.1, 0.0, 0.1), rpy=(0.0, 0.6, 0.0))
     depth = s.render()              # (num_envs, 48, 64) float32 on the device, planar depth in [near, far]
+
+That image is a perfect sensor's, of this instant.  ``DepthSensor(..., noise=DepthNoise(sigma2=0.005, p_drop=0.01,
+p_edge=0.5), latency=(1, 3))`` puts a real one's faults behind it in one more launch (t1render_depth_model,
+csrc/t1render_depth_model.hip): noise that grows with the square of the depth, pixels without a measurement, and a
+per-env delay of whole frames; render() then returns ``self.measured`` and ``self.depth`` stays the clean image.
 """
 import struct
 import zlib
@@ -235,6 +240,27 @@ def rpy_quat(roll, pitch, yaw):
             float(cr * cp * sy - sr * sp * cy), float(cr * cp * cy + sr * sp * sy))
 
 
+SEED_SALT = 0x5EED0DE7   # the model's seed is seed ^ SEED_SALT: its draws never coincide with the env step's
+
+
+class DepthNoise:
+    """The measurement model of t1render_depth_model (include/t1render.h states it to the bit).  sigma0, sigma2: the
+    noise's standard deviation [m] is sigma0 + sigma2 z^2 at depth z, as a stereo pair's; p_drop: the probability that a
+    pixel has no measurement; p_edge: the same for a pixel on the far side of an occlusion edge, where its depth exceeds
+    its nearest 4-neighbour's mn by more than edge_abs + edge_rel mn; fill: the value of a pixel without a measurement
+    (None: the sensor's far, what a pixel with nothing in range holds).  The defaults change nothing."""
+
+    def __init__(self, sigma0=0.0, sigma2=0.0, p_drop=0.0, p_edge=0.0, edge_abs=0.05, edge_rel=0.05, fill=None):
+        self.sigma0, self.sigma2, self.p_drop, self.p_edge = float(sigma0), float(sigma2), float(p_drop), float(p_edge)
+        self.edge_abs, self.edge_rel = float(edge_abs), float(edge_rel)
+        self.fill = None if fill is None else float(fill)
+
+    def pack(self, seed, env_base, near, far):
+        return _lib.RenderDepthNoise((int(seed) ^ SEED_SALT) & 0xFFFFFFFF, int(env_base), float(near), float(far),
+                                     self.sigma0, self.sigma2, self.p_drop, self.p_edge, self.edge_abs, self.edge_rel,
+                                     float(far) if self.fill is None else self.fill)
+
+
 class DepthSensor:
     """A depth camera bolted to body ``body`` of every env's robot (t1render_depth): one launch writes
     ``self.depth`` (num_envs, height, width), the planar depth [m] of the nearest surface in [near, far] and exactly
@@ -248,10 +274,19 @@ class DepthSensor:
     torch only where it needs it), or torch.float16 (the fp32 value rounded once).  ids=True also allocates ``self.ids`` (int8: -1 nothing in range, 0 terrain, 1 + body).  mounts: None, or a
     (num_envs, 7) float32 device tensor of pos and unit quat per env that replaces the mount env by env (kept by
     reference: write into it to re-randomise).  After a real-dynamics step an env that was reset is seen from where it
-    fell (rigid_state holds the pre-reset pose)."""
+    fell (rigid_state holds the pre-reset pose).
+
+    noise (a DepthNoise) and latency (lo, hi), in frames: with noise None and latency (0, 0) -- the default -- the sensor
+    is the perfect one above and has none of the following.  Otherwise render() makes a second launch
+    (t1render_depth_model) and returns ``self.measured`` (the shape and dtype of ``self.depth``, which stays the clean
+    image): the measurement of env n as it was ``self.lag[n]`` render() calls ago.  ``self.lag`` (num_envs,) int32 is
+    drawn once, uniformly in [lo, hi], from a torch.Generator seeded with ``seed``, and read by reference at every
+    render: write into it to re-randomise (values are clamped to [0, hi]).  With hi > 0 the sensor owns a ring of hi + 1
+    frames.  seed and env_base (a rank's first global env) key the model's draws together with the frame counter
+    ``self.frame``, which render() advances."""
 
     def __init__(self, env, width, height, pos, quat=None, rpy=None, body=0, vfov=DEFAULT_VFOV, near=0.1, far=3.0,
-                 dtype=None, prims=None, ids=False, mounts=None):
+                 dtype=None, prims=None, ids=False, mounts=None, noise=None, latency=(0, 0), seed=0, env_base=0):
         import torch
         dtype = torch.float32 if dtype is None else dtype
         if dtype not in (torch.float32, torch.float16):
@@ -275,20 +310,54 @@ class DepthSensor:
         self.mounts = mounts
         self.depth = torch.zeros(n, self.height, self.width, dtype=dtype, device=d)
         self.ids = torch.zeros(n, self.height, self.width, dtype=torch.int8, device=d) if ids else None
+        lo, hi = (int(x) for x in latency)
+        if not 0 <= lo <= hi < _lib.RENDER_DEPTH_MAXRING:
+            raise ValueError(f"latency must be 0 <= lo <= hi <= {_lib.RENDER_DEPTH_MAXRING - 1} frames, got {latency}")
+        self._model = None
+        if noise is None and hi == 0:
+            return
+        self.noise = DepthNoise() if noise is None else noise
+        self._model = self.noise.pack(seed, env_base, self.near, self.far)
+        self.measured = torch.zeros_like(self.depth)
+        g = torch.Generator().manual_seed(int(seed))
+        self.lag = torch.randint(lo, hi + 1, (n,), generator=g, dtype=torch.int32).to(d)
+        self._ring = torch.zeros(hi + 1, n, self.height, self.width, dtype=dtype, device=d) if hi > 0 else None
+        self._all_fresh = torch.ones(n, dtype=torch.uint8, device=d)
+        self.frame = 0
 
-    def render(self, stream=None):
-        """One launch on ``stream`` (a raw stream handle; None: torch's current stream of the env's device), no
-        allocation.  Returns self.depth; self.ids is written too when it exists."""
+    def render(self, stream=None, fresh=None):
+        """On ``stream`` (a raw stream handle; None: torch's current stream of the env's device), no allocation.  The
+        perfect sensor: one launch; returns self.depth (self.ids is written too when it exists), fresh is ignored.  With a
+        model: a second launch behind it; returns self.measured.  fresh: None, or a bool / uint8 (num_envs,) device tensor
+        of the envs whose history ends here (reset since the last render): they are served this frame now and nothing
+        older later.  The first call makes every env fresh."""
         env = self.env
         if stream is None:
             import torch
             stream = torch.cuda.current_stream(env.device).cuda_stream
+        if self._model is not None and fresh is not None and self.frame > 0:
+            import torch
+            if tuple(fresh.shape) != (self.depth.shape[0],) or fresh.dtype not in (torch.bool, torch.uint8) or \
+                    not fresh.is_contiguous() or fresh.device != self.depth.device:
+                raise ValueError(f"fresh must be a contiguous bool or uint8 ({self.depth.shape[0]},) tensor on "
+                                 f"{self.depth.device}")
         _lib.check(env._lib.t1render_depth(env._handle, _lib.C.byref(self._sensor),
                                            self.mounts.data_ptr() if self.mounts is not None else None, self._prims,
                                            len(self.prims), self.width, self.height, self.flags, self.depth.data_ptr(),
                                            self.ids.data_ptr() if self.ids is not None else None, stream),
                    "t1render_depth")
-        return self.depth
+        if self._model is None:
+            return self.depth
+        fresh = self._all_fresh if self.frame == 0 else fresh
+        ring = self._ring
+        _lib.check(env._lib.t1render_depth_model(_lib.C.byref(self._model), self.depth.data_ptr(), self.depth.shape[0],
+                                                 self.width, self.height, self.flags, self.frame & 0xFFFFFFFF,
+                                                 ring.data_ptr() if ring is not None else None,
+                                                 ring.shape[0] if ring is not None else 1, self.lag.data_ptr(),
+                                                 fresh.data_ptr() if fresh is not None else None,
+                                                 self.measured.data_ptr(), stream), "t1render_depth_model")
+        self.frame += 1
+        return self.measured
 
 
 def write_png(path, hwc_uint8):
